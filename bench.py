@@ -22,8 +22,12 @@ a barrier + MAX-over-ranks of the timed region.  Under torch.distributed.run the
 WORLD_SIZE must equal --gpus; without one, `bench.py --gpus N` starts the N rank processes itself
 (self_launch) before anything touches the GPU.
 
-Prints ONE JSON line (rank 0).  Also reports the dominant kernel's roofline
-(algorithmic bytes / measured kernel time vs 8 TB/s HBM peak) and the CPU
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the
+line: the headline rate, ms_per_step and the dominant kernel's roofline from the timed region
+(algorithmic bytes / measured kernel time vs 8 TB/s HBM peak).  --dump-outputs DIR also writes what
+the last timed step computed as DIR/<name>.npy (the inputs are seeded: the same arguments give the
+same problems, so two builds can be compared output for output).  --full adds the legs that take
+runs of their own: the isolated-launch kernel time, the host-array end-to-end rate and the CPU
 baseline (the oracle restatement of the reference algorithm on host cores).
 """
 import argparse
@@ -307,6 +311,31 @@ def make_problems(workload, N, K, B, seed0, pattern="generator"):
     return values, mask, times
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_rows(B, bytes_per_row, max_bytes=DUMP_MAX_BYTES, seed=DUMP_SAMPLE_SEED):
+    """The batch rows --dump-outputs writes: all of them while the arrays fit max_bytes together,
+    otherwise a fixed sample (seeded, sorted, the same for every array and every run)."""
+    keep = max(1, max_bytes // bytes_per_row)
+    if keep >= B:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(seed).choice(B, size=keep, replace=False))
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """Write the timed path's outputs (name -> host array [B, ...], f64) as path/<name>.npy, rank r > 0
+    of a multi-GPU run as path/<name>_rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    B = len(next(iter(arrays.values())))
+    # (1 kB per file set aside for the .npy header, so the files stay within the limit together)
+    rows = dump_rows(B, sum(a[0].nbytes for a in arrays.values()), DUMP_MAX_BYTES - 1024 * len(arrays))
+    for name, a in arrays.items():
+        f = name if world == 1 or rank == 0 else "%s_rank%d" % (name, rank)
+        np.save(os.path.join(path, f + ".npy"), np.ascontiguousarray(a[rows], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -326,11 +355,19 @@ def main():
     ap.add_argument("--timing-stride", type=int, default=0,
                     help="also sample every n-th step's kernel with its own HIP event pair (0: none; the "
                          "sampled launches add event overhead to the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the arrays a caller of "
+                         "the timed path receives) as DIR/<name>.npy, float64, at most 64 MB in all (a fixed "
+                         "seeded sample of the batch where it is larger)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the isolated-launch kernel time, the "
+                         "host-array end-to-end rate and the CPU baseline (each a run of its own)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-sample", type=int, default=20000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-end-to-end", action="store_true",
-                    help="skip the host-array leg (profiling runs: the trace then holds only the bench's own grid)")
+                    help="with --full: skip the host-array leg (profiling runs: the trace then holds only the "
+                         "bench's own grid)")
     ap.add_argument("--split", action="store_true", help="two-kernel path (assembly + block Cholesky)")
     ap.add_argument("--general-kernel", action="store_true",
                     help="force the general LDS-resident fused kernel (A/B against the default)")
@@ -382,9 +419,11 @@ def main():
     # the kernel's steady-state duration.  Optionally (--timing-stride n) every n-th step goes through
     # a second context that carries an event pair in the dispatch packet; events cost ~4.5 us of GPU
     # time per launch at config 2 (scripts/host_overhead.py), charged to `value`, so this is off by
-    # default.  After the region, launches that each carry their own event pair give the duration of
-    # a launch that does not overlap its predecessor (reported as kernel_ms_isolated).
-    ctx_t = mtg.Context(local)
+    # default.  After the region (--full), launches that each carry their own event pair give the
+    # duration of a launch that does not overlap its predecessor (reported as kernel_ms_isolated).
+    # The second context exists only where one of the two needs it.
+    stride = args.timing_stride
+    ctx_t = mtg.Context(local) if (stride > 0 or args.full) else None
     stream = torch.cuda.current_stream(dev)
     if wl == "config5":
         # solve once (untimed) for the free derivatives, then time the candidate-cost sweep
@@ -396,22 +435,22 @@ def main():
         out_d = torch.empty((B, C5_CANDIDATES), dtype=torch.float64, device=dev)
         jac_d = torch.empty((B, C5_CANDIDATES, K), dtype=torch.float64, device=dev)
         step = ctx.jacobian_call(N, r, x_d, t_d, s_d, out_d, jac_d)
-        step_t = ctx_t.jacobian_call(N, r, x_d, t_d, s_d, out_d, jac_d)
+        step_t = ctx_t.jacobian_call(N, r, x_d, t_d, s_d, out_d, jac_d) if ctx_t is not None else None
         kname = "time_jacobian_kernel"
     else:
         out_d = torch.empty((B, K, D, N), dtype=torch.float64, device=dev)
         # one step = one launch of the solve on torch's current stream
         kw = dict(split=args.split, general=args.general_kernel, dl=args.dl_kernel, column=args.column_kernel)
         step = ctx.solve_call(N, r, v_d, m_d, t_d, out_d, **kw)
-        step_t = ctx_t.solve_call(N, r, v_d, m_d, t_d, out_d, **kw)
+        step_t = ctx_t.solve_call(N, r, v_d, m_d, t_d, out_d, **kw) if ctx_t is not None else None
         nat = mtg._native
         kflags = ((nat.MTG_FLAG_SPLIT_KERNELS if args.split else 0) | (nat.MTG_FLAG_GENERAL_KERNEL if args.general_kernel else 0)
                   | (nat.MTG_FLAG_DL_KERNEL if args.dl_kernel else 0) | (nat.MTG_FLAG_COLUMN_KERNEL if args.column_kernel else 0))
         kname = mtg._native.solve_kernel(N, D, K, r, kflags, B=B)
-    stride = args.timing_stride
     timed_steps = [i for i in range(args.steps) if stride > 0 and i % stride == 0]
     ctx.enable_timing(0)
-    ctx_t.enable_timing(max(len(timed_steps), 1))
+    if ctx_t is not None:
+        ctx_t.enable_timing(max(len(timed_steps), 1))
     plan = [step_t if stride > 0 and i % stride == 0 else step for i in range(args.steps)]
 
     # warmup: at least --warmup steps AND at least --min-warmup-ms of wall time
@@ -445,18 +484,28 @@ def main():
     kern_ms = gpu_ms / args.steps
     # (A sampled launch's own event interval inside the region starts while its predecessor is still
     # draining, so it reads longer than the per-step time: config 2, 20.1 vs 18.8 us.)
-    n_iso = 32
-    ctx_t.enable_timing(n_iso)
-    for _ in range(n_iso):
-        step_t()
-    torch.cuda.synchronize(dev)
-    iso = ctx_t.kernel_times_ms(n_iso)
     el = max_over_ranks(el, dist if world > 1 else None)
 
-    # spot check of the timed outputs (finite) -- not timed
-    assert np.isfinite(out_d.cpu().numpy()).all(), "non-finite outputs"
+    # the timed outputs as the last timed step left them: spot check (finite) and --dump-outputs -- not timed
     if wl == "config5":
-        assert np.isfinite(jac_d.cpu().numpy()).all(), "non-finite Jacobian"
+        outputs = {"cost": out_d.cpu().numpy(), "time_jacobian": jac_d.cpu().numpy()}
+        assert np.isfinite(outputs["cost"]).all(), "non-finite outputs"
+        assert np.isfinite(outputs["time_jacobian"]).all(), "non-finite Jacobian"
+    else:
+        outputs = {"coeffs": out_d.cpu().numpy()}
+        assert np.isfinite(outputs["coeffs"]).all(), "non-finite outputs"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs, rank, world)
+    del outputs
+
+    iso = None
+    if args.full:
+        n_iso = 32
+        ctx_t.enable_timing(n_iso)
+        for _ in range(n_iso):
+            step_t()
+        torch.cuda.synchronize(dev)
+        iso = ctx_t.kernel_times_ms(n_iso)
 
     if wl == "config5":
         units = B * C5_CANDIDATES
@@ -515,17 +564,18 @@ def main():
                      "kernel_ms": kern_ms,
                      "kernel_ms_method": "HIP events around the timed region on the launch stream / steps "
                      "(back-to-back launches)",
-                     "kernel_ms_isolated": float(np.mean(iso)), "kernel_ms_isolated_min": float(np.min(iso)),
+                     "kernel_ms_isolated": float(np.mean(iso)) if iso is not None else None,
+                     "kernel_ms_isolated_min": float(np.min(iso)) if iso is not None else None,
                      "kernel_ms_sampled": float(np.mean(per_launch)) if len(per_launch) else None,
                      "kernel_launches_sampled": len(per_launch), "gpu_ms_timed_region": gpu_ms,
                      "algorithmic_bytes_per_traj": bpt},
         "cpu_baseline": None,
     }
-    # end-to-end (not `value`): host arrays in and out through the C ABI's staging -- H2D, kernel,
+    # --full, end-to-end (not `value`): host arrays in and out through the C ABI's staging -- H2D, kernel,
     # D2H, synchronize -- the PCIe-inclusive rate of a caller that holds its batch in host memory
-    if wl != "config5" and not args.no_end_to_end:
+    if args.full and wl != "config5" and not args.no_end_to_end:
         out["end_to_end"] = end_to_end(ctx, N, r, values, mask, times, unit, bpt - K * D * N * 8, K * D * N * 8)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # (the CPU baseline is an N = 1 figure)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:  # (the CPU baseline is an N = 1 figure)
         host = host_cpu_info()
         threads = int(os.environ.get("MTG_CPU_THREADS", host["usable_cpus"]))
         S = min(args.cpu_sample, B)
@@ -543,7 +593,8 @@ def main():
         out["cpu_baseline"] = {"value": rate, "unit": unit, "cores": threads, "kind": "port", "sample": sample,
                                "host": host}
     ctx.close()
-    ctx_t.close()
+    if ctx_t is not None:
+        ctx_t.close()
     if rank == 0:
         print(json.dumps(out))
     if world > 1:

@@ -11,7 +11,7 @@ rc=$?
 grep -E "^FAILED|^ERROR| passed| failed" $O/pytest_gpu.log | tail -20
 [ $rc -le 1 ] || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { cat $O/smoke.log; exit 1; }
-b() { f=$O/$1.json; shift; timeout -k 10 400 python bench.py "$@" > $f 2> $f.err || { tail $f.err; exit 1; }; }
+b() { f=$O/$1.json; shift; timeout -k 10 400 python bench.py --full "$@" > $f 2> $f.err || { tail $f.err; exit 1; }; }
 b bench_c2
 b bench_20_5 --steps 20 --warmup 5
 b bench_c3 --batch 125000 --steps 100 --warmup 50 --no-cpu-baseline

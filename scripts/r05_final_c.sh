@@ -14,6 +14,6 @@ for v in default column; do
   x=""; [ $v = column ] && x="--column-kernel"
   OUT=gpurun_out/prof_accel_${v}$T; mkdir -p $OUT
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- \
-      python3 bench.py --no-cpu-baseline --no-end-to-end --pattern accel-ends $x > $OUT/bench.log 2>&1 || exit $?
+      python3 bench.py --full --no-cpu-baseline --no-end-to-end --pattern accel-ends $x > $OUT/bench.log 2>&1 || exit $?
 done
 echo OK > gpurun_out/prof_done_$T

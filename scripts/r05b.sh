@@ -14,7 +14,7 @@ for r in 1 2; do
   for v in default "$@"; do
     for p in ${PATTERNS:-generator accel-ends interior-vel}; do
       f=$O/bench_${v}_${p}_$r.json
-      MTG_LIBRARY=$(lib $v) timeout -k 10 200 python bench.py --steps 200 --warmup 100 --no-cpu-baseline --no-end-to-end --pattern $p $BENCHX > $f 2> $f.err || { tail $f.err; exit 1; }
+      MTG_LIBRARY=$(lib $v) timeout -k 10 200 python bench.py --full --steps 200 --warmup 100 --no-cpu-baseline --no-end-to-end --pattern $p $BENCHX > $f 2> $f.err || { tail $f.err; exit 1; }
       python -c "import json; d=json.load(open('$f')); r=d['roofline']; print('$v $p', r['kernel'], 'kernel_ms %.4f' % r['kernel_ms'], 'frac %.3f' % r['frac'])"
     done
   done

@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/${EVID:-r06j}
 mkdir -p $O
 export TMPDIR=/tmp
-b() { f=$O/$1.json; shift; timeout -k 10 400 python bench.py "$@" > $f 2> $f.err || { tail $f.err; exit 1; }; }
+b() { f=$O/$1.json; shift; timeout -k 10 400 python bench.py --full "$@" > $f 2> $f.err || { tail $f.err; exit 1; }; }
 b bench_c2
 b bench_c3 --batch 125000 --steps 100 --warmup 50 --no-cpu-baseline
 b bench_c4 --workload config4

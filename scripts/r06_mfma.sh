@@ -13,7 +13,7 @@ for grp in "SQ_INSTS_VALU_MFMA_F64 SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_W
            "SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_INSTS_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES"; do
   i=$((i+1))
   timeout -k 10 240 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/p$i -o run -- \
-      python3 bench.py --workload config5 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/p$i.log 2>&1 || exit $?
+      python3 bench.py --full --workload config5 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/p$i.log 2>&1 || exit $?
   rm -f $OUT/p$i/run_kernel_trace.csv
 done
 echo OK > gpurun_out/${T}_done

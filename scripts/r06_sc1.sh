@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 run() {  # tag policy args...
   t=$1; p=$2; shift 2
   f=$O/${t}_sc$p.json
-  MTG_DL_STORE_SC1=$p timeout -k 10 200 python bench.py --steps 100 --warmup 50 --no-cpu-baseline --no-end-to-end "$@" > $f 2> $f.err || { tail $f.err; exit 1; }
+  MTG_DL_STORE_SC1=$p timeout -k 10 200 python bench.py --full --steps 100 --warmup 50 --no-cpu-baseline --no-end-to-end "$@" > $f 2> $f.err || { tail $f.err; exit 1; }
   python -c "import json; d=json.load(open('$f')); r=d['roofline']; print('$t sc1=$p', 'kernel_us %.2f' % (r['kernel_ms']*1e3), 'frac %.3f' % r['frac'])"
 }
 for B in ${BATCHES:-10000 20000 30000 40000 50000 70000 100000}; do

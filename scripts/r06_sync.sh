@@ -10,7 +10,7 @@ for r in 1 2 3; do
   for v in default poll; do
     f=$O/bench_${v}_$r.json
     if [ $v = poll ]; then export HSA_ENABLE_INTERRUPT=0; else unset HSA_ENABLE_INTERRUPT; fi
-    timeout -k 10 200 python bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-end-to-end > $f 2> $f.err || { tail $f.err; exit 1; }
+    timeout -k 10 200 python bench.py --full --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-end-to-end > $f 2> $f.err || { tail $f.err; exit 1; }
     python -c "import json; d=json.load(open('$f')); r=d['roofline']; print('$v', 'ms_per_step %.4f' % (d['ms_per_step']*1e3), 'kernel_ms %.4f' % (r['kernel_ms']*1e3), 'iso %.4f' % (r['kernel_ms_isolated']*1e3), 'value %.4g' % d['value'])"
   done
 done

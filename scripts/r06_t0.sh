@@ -13,6 +13,6 @@ for r in 1 2 3 4; do
     python -c "import json; d=json.load(open('$f')); r=d['roofline']; print('$v', 'ms_per_step %.3f' % (d['ms_per_step']*1e3), 'kernel_us %.3f' % (r['kernel_ms']*1e3), 'value %.4g' % d['value'])"
   done
 done
-timeout -k 10 300 python bench.py --gpus 2 --steps 50 --warmup 20 --no-cpu-baseline --no-end-to-end > $O/bench_gpus2.json 2> $O/bench_gpus2.err || { tail $O/bench_gpus2.err; exit 1; }
+timeout -k 10 300 python bench.py --full --gpus 2 --steps 50 --warmup 20 --no-cpu-baseline --no-end-to-end > $O/bench_gpus2.json 2> $O/bench_gpus2.err || { tail $O/bench_gpus2.err; exit 1; }
 cat $O/bench_gpus2.json | cut -c1-300
 echo OK > $O/done

@@ -12,7 +12,7 @@ timeout -k 10 900 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -v --ti
 rc=$?
 grep -E "^FAILED|^ERROR| passed| failed|PASSED|FAILED" $O/pytest_dl.log | tail -80
 [ $rc -eq 0 ] || exit $rc
-b() { f=$O/$1.json; shift; timeout -k 10 300 python bench.py --no-cpu-baseline --no-end-to-end "$@" > $f 2> $f.err || { tail $f.err; exit 1; }; }
+b() { f=$O/$1.json; shift; timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-end-to-end "$@" > $f 2> $f.err || { tail $f.err; exit 1; }; }
 b bench_c2
 b bench_c2_accel --pattern accel-ends
 b bench_c2_accel_column --pattern accel-ends --column-kernel

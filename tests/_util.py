@@ -9,16 +9,34 @@ GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 def golden_cases():
     """The truth fixtures (tests/golden/make_golden.py); host_solve_bitwise.npz, the truth samples
-    config4_truth_sample.npz / accel12_truth_sample.npz and offpattern_truth_n12.npz are fixtures of
-    their own (tests/golden/make_host_fixture.py, make_config4_truth.py, make_offpattern_truth.py)."""
-    own = ("host_solve_bitwise.npz", "config4_truth_sample.npz", "accel12_truth_sample.npz", "offpattern_truth_n12.npz")
+    config4_truth_sample (two pieces) / accel12_truth_sample.npz and offpattern_truth_n12 (two pieces)
+    are fixtures of their own (tests/golden/make_host_fixture.py, make_config4_truth.py, make_offpattern_truth.py)."""
+    own = ("host_solve_bitwise", "config4_truth_sample", "accel12_truth_sample", "offpattern_truth_n12")
     return sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz"))
-                  if os.path.basename(p) not in own)
+                  if os.path.basename(p).split(".")[0] not in own)
 
 
 def load_golden(name):
     z = np.load(os.path.join(GOLDEN_DIR, name + ".npz"), allow_pickle=False)
     return {k: z[k] for k in z.files}
+
+
+def save_pieces(name, pieces, **arrays):
+    """Store a fixture as golden/<name>.<i>of<pieces>.npz (a fixture that would pass 1 MiB as one
+    file): piece i holds the i-th part of every array split along its first axis (np.array_split)
+    and a copy of every scalar."""
+    for i in range(pieces):
+        np.savez_compressed(os.path.join(GOLDEN_DIR, "%s.%dof%d.npz" % (name, i + 1, pieces)),
+                            **{k: a if a.ndim == 0 else np.array_split(a, pieces)[i] for k, a in arrays.items()})
+
+
+def load_pieces(name, pieces):
+    """The fixture save_pieces stored, its arrays joined again."""
+    z = [np.load(os.path.join(GOLDEN_DIR, "%s.%dof%d.npz" % (name, i + 1, pieces)), allow_pickle=False)
+         for i in range(pieces)]
+    for p in z[1:]:
+        assert p.files == z[0].files
+    return {k: z[0][k] if z[0][k].ndim == 0 else np.concatenate([p[k] for p in z]) for k in z[0].files}
 
 
 def to_abi(values_nd, mask32, N):

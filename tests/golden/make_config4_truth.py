@@ -3,7 +3,7 @@
 polynomial_optimization_linear_impl.h:329-369 evaluated in mpmath) for a random sample of the
 trajectories of a full-size 1e4 batch.
 
-  config4 -> config4_truth_sample.npz: N = 12, K = 20, JERK; the bench's config-4 generator,
+  config4 -> config4_truth_sample (.1of2.npz, .2of2.npz: one file would pass 1 MiB): N = 12, K = 20, JERK; the bench's config-4 generator,
              createRandomVertices(SNAP, 20, [-10,-20,-10], [10,20,10]) + estimateSegmentTimes(3, 5),
              seed0 = 0; 256 trajectories (the DL kernel's long-chain pattern pass).
   accel12 -> accel12_truth_sample.npz: N = 12, K = 20, JERK with the ends fixed only to ACCELERATION,
@@ -25,15 +25,16 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
 N, K, r, B, S = 12, 20, 3, 10000, 256
 
 CASES = {
     "config4": dict(lo=[-10.0, -20.0, -10.0], hi=[10.0, 20.0, 10.0], seed0=0, max_derivative=4, S=256,
-                    sample_seed=20, file="config4_truth_sample.npz"),
+                    sample_seed=20, name="config4_truth_sample", pieces=2),
     "accel12": dict(lo=[-50.0] * 3, hi=[50.0] * 3, seed0=500, max_derivative=2, S=96, sample_seed=21,
-                    file="accel12_truth_sample.npz"),
+                    name="accel12_truth_sample", pieces=1),
 }
 
 
@@ -61,14 +62,26 @@ def _one(args):
     return truth_solve(N, r, *args)[0]
 
 
+def load(case="config4"):
+    """The stored fixture: index, coeffs, inputs_sha256."""
+    from _util import load_golden, load_pieces
+    c = CASES[case]
+    return load_golden(c["name"]) if c["pieces"] == 1 else load_pieces(c["name"], c["pieces"])
+
+
 def main(case="config4"):
     vals, mask, times = batch(case)
     idx = sample_index(case)
     with Pool(int(os.environ.get("JOBS", "8"))) as p:
         tr = p.map(_one, [(vals[b], mask[b], times[b]) for b in idx], chunksize=1)
-    np.savez_compressed(os.path.join(HERE, CASES[case]["file"]), index=idx,
-                        coeffs=np.stack(tr).astype(np.float64),
-                        inputs_sha256=np.array(inputs_digest(vals, mask, times, idx)))
+    from _util import save_pieces
+    c = CASES[case]
+    out = dict(index=idx, coeffs=np.stack(tr).astype(np.float64),
+               inputs_sha256=np.array(inputs_digest(vals, mask, times, idx)))
+    if c["pieces"] == 1:
+        np.savez_compressed(os.path.join(HERE, c["name"] + ".npz"), **out)
+    else:
+        save_pieces(c["name"], c["pieces"], **out)
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fixture offpattern_truth_n12.npz: 60-digit truth (make_golden.truth_solve, the reference algorithm
+"""Fixture offpattern_truth_n12 (.1of2.npz, .2of2.npz): 60-digit truth (make_golden.truth_solve, the reference algorithm
 of polynomial_optimization_linear_impl.h:329-369 in mpmath) for the first S = 64 trajectories of each
 N = 12 / K = 20 off-pattern batch of test_gpu_parity.test_dl_off_pattern_masks_vs_general_kernel
 (tests/_util.off_pattern_batch, B = 437, seed 900 + N + D).  At N = 12 the FP64 reference algorithm is
@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
 N, K, r, B, S = 12, 20, 3, 437, 64
 CASES = [(3, "random"), (3, "accel"), (3, "ends"), (4, "mixed")]
-FILE = os.path.join(HERE, "offpattern_truth_n12.npz")
+NAME, PIECES = "offpattern_truth_n12", 2  # (two files: one would pass 1 MiB; tests/_util.load_pieces)
 
 
 def batch(D, kind):
@@ -53,7 +53,8 @@ def main():
         tr = p.map(_one, jobs, chunksize=1)
     for i, (D, kind) in enumerate(CASES):
         out["%s_d%d_coeffs" % (kind, D)] = np.stack(tr[i * S:(i + 1) * S]).astype(np.float64)
-    np.savez_compressed(FILE, **out)
+    from _util import save_pieces
+    save_pieces(NAME, PIECES, **out)
 
 
 if __name__ == "__main__":

@@ -1251,7 +1251,7 @@ def test_config4_full_size_truth_sample(gpu_ctx):
     from mav_trajectory_generation_cmake_amd import _native as nat
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
     import make_config4_truth as m
-    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "config4_truth_sample.npz"))
+    g = m.load()
     vals, mask, times = m.batch()
     idx = g["index"]
     assert len(idx) == 256 and m.inputs_digest(vals, mask, times, idx) == str(g["inputs_sha256"])
@@ -1301,7 +1301,8 @@ def _n12_truth(kind, D, vals, mask, times):
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
     import make_offpattern_truth as m
-    g = np.load(m.FILE)
+    from _util import load_pieces
+    g = load_pieces(m.NAME, m.PIECES)
     assert m.digest(vals, mask, times) == str(g["%s_d%d_sha256" % (kind, D)]), "inputs changed: regenerate"
     return g["%s_d%d_coeffs" % (kind, D)]
 
@@ -1405,7 +1406,7 @@ def test_dl_ends_pass_n12_full_size_truth_sample(gpu_ctx):
     from mav_trajectory_generation_cmake_amd import _native as nat
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
     import make_config4_truth as m
-    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", m.CASES["accel12"]["file"]))
+    g = m.load("accel12")
     vals, mask, times = m.batch("accel12")
     idx = g["index"]
     assert len(idx) == 96 and m.inputs_digest(vals, mask, times, idx) == str(g["inputs_sha256"])

@@ -231,7 +231,7 @@ def test_host_solve_config4_truth_sample():
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, os.path.join(here, "golden"))
     import make_config4_truth as m
-    g = np.load(os.path.join(here, "golden", "config4_truth_sample.npz"))
+    g = m.load()
     vals, mask, times = m.batch()
     idx = g["index"]
     assert np.array_equal(idx, m.sample_index())
