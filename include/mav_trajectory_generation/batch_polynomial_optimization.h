@@ -145,6 +145,16 @@ class BatchPolynomialOptimization {
                                   grad, flags),
           ctx_, "mtg_cost_at_times_batch");
   }
+  // collision cost (and gradient, packed as costAtTimes' grad) over a signed distance field
+  // (mtg_collision_cost_batch: getCostAndGradientCollision, nl_impl:1523-1709); D must be 3
+  void collisionCost(int64_t batch, const double* vertex_values, const uint8_t* mask, const double* times,
+                     const mtg_sdf_grid& grid, const mtg_collision_params& params, double* cost, double* grad = nullptr,
+                     uint8_t* is_collision = nullptr, int32_t* n_evaluated = nullptr, int32_t* status = nullptr,
+                     unsigned flags = 0) {
+    check(mtg_collision_cost_batch(ctx_, N, D_, K_, batch, vertex_values, mask, times, &grid, &params, cost, grad,
+                                   is_collision, n_evaluated, status, flags),
+          ctx_, "mtg_collision_cost_batch");
+  }
   void coefficientsFromVertices(int64_t batch, const double* vertex_values, const double* times, double* coeffs,
                                 unsigned flags = 0) {
     check(mtg_coefficients_from_vertices_batch(ctx_, N, D_, K_, batch, vertex_values, times, coeffs, flags), ctx_,
@@ -182,6 +192,27 @@ class BatchPolynomialOptimization {
   std::vector<mtg_ctx*> ctxs_;
   mtg_ctx* ctx_ = nullptr;
 };
+
+// getCostAndGradientCollision for trajectories of N coefficients and K segments in three dimensions,
+// without a BatchPolynomialOptimization object: on the library's host path
+// (mtg_host_collision_cost_batch) unless the execution policy is kDevice, as the single-problem
+// calls of PolynomialOptimization<N> (runtime.h).  Host pointers.
+template <int N>
+inline void collisionCost(int K, int64_t batch, const double* vertex_values, const uint8_t* mask, const double* times,
+                          const mtg_sdf_grid& grid, const mtg_collision_params& params, double* cost,
+                          double* grad = nullptr, uint8_t* is_collision = nullptr, int32_t* n_evaluated = nullptr,
+                          int32_t* status = nullptr) {
+  if (singleOnDevice()) {
+    mtg_ctx* ctx = defaultContext();
+    check(mtg_collision_cost_batch(ctx, N, 3, K, batch, vertex_values, mask, times, &grid, &params, cost, grad,
+                                   is_collision, n_evaluated, status, 0),
+          ctx, "mtg_collision_cost_batch");
+  } else {
+    check(mtg_host_collision_cost_batch(N, 3, K, batch, vertex_values, mask, times, &grid, &params, cost, grad,
+                                        is_collision, n_evaluated, status, 1),
+          nullptr, "mtg_host_collision_cost_batch");
+  }
+}
 
 }  // namespace mav_trajectory_generation
 

@@ -291,6 +291,87 @@ int mtg_min_max_magnitude_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch
                                 const double* times, int derivative, uint32_t dimension_mask,
                                 mtg_extremum* minimum, mtg_extremum* maximum, unsigned flags);
 
+/* ---- Collision term of the nonlinear objective (kOptimizeFreeConstraintsAndCollision[AndTime]).
+ *
+ * The map.  The reference reads distances through esdf / sdf_tools, which are not part of its tree;
+ * this ABI takes a dense grid of signed distances instead:
+ *   cell of p            i = floor((p - origin) / resolution) per axis
+ *   centre of cell i     origin + (i + 0.5) * resolution
+ *   nearest-cell lookup  distance[cell of p], or oob_distance when an index is outside the grid
+ *                        (stands for getDistanceInMetricUnits / Get)
+ *   continuous lookup    getDistanceSDF (nl_impl:1846-1904): the eight cells at index +-1 on every
+ *                        axis around the cell of p (a stencil two cells wide, getNeighborsSDF
+ *                        :1808-1843), their centres as corner positions, combined by triLerp exactly
+ *                        as written (:2436-2464); the nearest-cell value when a corner cell is
+ *                        outside the grid. */
+typedef struct mtg_sdf_grid {
+  const float* distance;   /* [nx][ny][nz], z fastest; host or device pointer as the call's flags say */
+  int32_t nx, ny, nz;
+  double origin[3];        /* metric position of the low corner of cell (0,0,0) */
+  double resolution;       /* cell edge, > 0 */
+  double oob_distance;     /* value returned for a cell outside the grid */
+} mtg_sdf_grid;
+
+/* The reference's optimization_parameters_ fields the collision term reads. */
+typedef struct mtg_collision_params {
+  double coll_check_time_increment;  /* dt of the sample clock, > 0 */
+  double map_resolution;             /* arc-length gate, bounds margin and finite-difference increment,
+                                        >= 0; separate from grid.resolution */
+  double epsilon;                    /* width of the quadratic band of the potential */
+  double robot_radius;
+  double coll_pot_multiplier;
+  double min_bound[3], max_bound[3];
+  int32_t use_continuous_distance;   /* use_continous_distance: the continuous lookup inside the bounds */
+  int32_t reserved;
+} mtg_collision_params;
+
+/* Batched getCostAndGradientCollision (nl_impl:1523-1709) with getCostAndGradientPotentialESDF
+ * (:1713-1806), getDistanceSDF and getCostPotential (:2319-2343), restated exactly.  D must be 3 and
+ * N one of 6, 8, 10, 12; any K >= 1.  Per trajectory, with time_sum = -1, dist_sum = 0:
+ *   for each segment i: for (t = 0; t < T_i; t += dt)      (the accumulated clock, not j * dt)
+ *     position and velocity of the three axes at t;
+ *     time_sum < 0: time_sum = 0, prev_pos = pos, next sample;
+ *     time_sum += dt, dist_sum += |pos - prev_pos|, prev_pos = pos;
+ *     dist_sum < map_resolution: next sample;
+ *     c, grad c = potential and its central differences at pos (increment map_resolution);
+ *     J += c |vel| time_sum;  the gradient below only if |vel| > 1e-6;  dist_sum = time_sum = 0
+ *   after the segment: time_sum += -dt + (T_i - t)   (t: the first clock value not below T_i; this
+ *     can leave time_sum in (-dt, 0], and the next sample then takes the first-entry branch again)
+ * Potential of d = distance - robot_radius: d <= 0: coll_pot_multiplier (-d) + epsilon / 2 and the
+ * trajectory's collision flag is set; d <= epsilon: (d - epsilon)^2 / (2 epsilon); else 0.  The
+ * continuous lookup is used when use_continuous_distance is set and every axis of pos lies in
+ * [min_bound + map_resolution, max_bound - map_resolution], the nearest-cell lookup otherwise.
+ * Gradient (paper eq. 14, nl_impl:1671-1687): a sample of segment i adds, per axis k, to that
+ * segment's coefficient-space vector
+ *   |vel| time_sum (grad c)_k [t^n] + time_sum c vel_k / |vel| [n t^(n-1)],   n = 0 .. N-1,
+ * and the reference's product with L_pp is A(T_i)^-T applied to it, top half to vertex i, bottom
+ * half to vertex i + 1 (summed at an interior vertex), free derivatives in the reference's
+ * (vertex, derivative) order: the packing of mtg_cost_at_times_batch's grad_out, so the two add.
+ * map_resolution == 0 divides by zero in the central differences, as in the reference (NaN gradient).
+ *
+ * vertex_values [B][V][h][D] holds ALL derivatives; the coefficients are formed from them as
+ * mtg_coefficients_from_vertices_batch does.  fixed_mask [B][V] is needed only for grad_out.
+ * cost_out [B]; grad_out [B][D][V*h] (nullable; entries >= n_free are 0); collision_out [B]
+ * (nullable); n_evaluated_out [B] (nullable): samples that reached the potential; status [B]
+ * (nullable).  A trajectory with a T_i that is not positive and finite, or with more than 2^24 clock
+ * samples in a segment (T_i / dt), gets MTG_TRAJ_BAD_TIME, a NaN cost and a zero gradient.
+ * MTG_ERR_INVALID_ARGUMENT: D != 3, dt <= 0, map_resolution < 0, grid resolution <= 0, a grid
+ * dimension < 1.  With MTG_FLAG_DEVICE_PTRS grid->distance is a device pointer too (grid and params
+ * themselves are always host structs, read during the call); a host-pointer call stages the grid
+ * once per call.  Results do not depend on the trajectory's place in the batch or on the batch. */
+int mtg_collision_cost_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* vertex_values,
+                             const uint8_t* fixed_mask, const double* times, const mtg_sdf_grid* grid,
+                             const mtg_collision_params* params, double* cost_out, double* grad_out,
+                             uint8_t* collision_out, int32_t* n_evaluated_out, int32_t* status, unsigned flags);
+
+/* Host (CPU) path of mtg_collision_cost_batch, no context and no GPU needed: the loop above in
+ * scalar C++ in the reference's order, on the calling thread(s).  The C++ drop-in uses it for single
+ * trajectories.  All host pointers; threads <= 0: mtg_host_default_threads(). */
+int mtg_host_collision_cost_batch(int N, int D, int K, int64_t batch, const double* vertex_values,
+                                  const uint8_t* fixed_mask, const double* times, const mtg_sdf_grid* grid,
+                                  const mtg_collision_params* params, double* cost_out, double* grad_out,
+                                  uint8_t* collision_out, int32_t* n_evaluated_out, int32_t* status, int threads);
+
 /* Timing of the most recent kernel launch(es) of this context on its stream
  * (hipEvent pair around the solve kernel), in milliseconds. */
 int mtg_last_kernel_ms(mtg_ctx* ctx, float* ms);

@@ -46,6 +46,22 @@ KERNEL_NAMES = {MTG_KERNEL_COLUMN: "solve_reg_kernel",
 
 _c_dp = ctypes.c_void_p  # every array argument is passed as a raw address
 
+
+class SdfGrid(ctypes.Structure):
+    """struct mtg_sdf_grid (include/mtg.h)."""
+    _fields_ = [("distance", ctypes.c_void_p), ("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nz", ctypes.c_int32),
+                ("origin", ctypes.c_double * 3), ("resolution", ctypes.c_double), ("oob_distance", ctypes.c_double)]
+
+
+class CollisionParams(ctypes.Structure):
+    """struct mtg_collision_params (include/mtg.h)."""
+    _fields_ = [("coll_check_time_increment", ctypes.c_double), ("map_resolution", ctypes.c_double),
+                ("epsilon", ctypes.c_double), ("robot_radius", ctypes.c_double),
+                ("coll_pot_multiplier", ctypes.c_double), ("min_bound", ctypes.c_double * 3),
+                ("max_bound", ctypes.c_double * 3), ("use_continuous_distance", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 _SIGNATURES = {
     "mtg_abi_version": (ctypes.c_int, []),
     "mtg_solve_kernel": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint]),
@@ -83,6 +99,14 @@ _SIGNATURES = {
     "mtg_cost_at_times_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_int64, _c_dp, _c_dp, _c_dp, ctypes.c_int,
                                                _c_dp, _c_dp, _c_dp, ctypes.c_uint]),
+    "mtg_collision_cost_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int64, _c_dp, _c_dp, _c_dp, ctypes.POINTER(SdfGrid),
+                                                ctypes.POINTER(CollisionParams), _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                                ctypes.c_uint]),
+    "mtg_host_collision_cost_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _c_dp,
+                                                     _c_dp, _c_dp, ctypes.POINTER(SdfGrid),
+                                                     ctypes.POINTER(CollisionParams), _c_dp, _c_dp, _c_dp, _c_dp,
+                                                     _c_dp, ctypes.c_int]),
     "mtg_time_jacobian_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_int64, _c_dp, _c_dp, ctypes.c_int, _c_dp,
                                                ctypes.c_double, _c_dp, _c_dp, ctypes.c_uint]),

@@ -935,6 +935,88 @@ int mtg_cost_at_times_batch(mtg_ctx* ctx, int N, int D, int K, int derivative_to
   return MTG_OK;
 }
 
+int mtg_collision_cost_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* vertex_values,
+                             const uint8_t* fixed_mask, const double* times, const mtg_sdf_grid* grid,
+                             const mtg_collision_params* params, double* cost_out, double* grad_out,
+                             uint8_t* collision_out, int32_t* n_evaluated_out, int32_t* status, unsigned flags) {
+  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
+  if (N < 6 || N > 12 || (N % 2)) return set_error(ctx, MTG_ERR_UNSUPPORTED_N, "N must be 6, 8, 10 or 12");
+  if (D != 3) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "the collision term needs D == 3");
+  if (K < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need K >= 1, batch >= 0");
+  if (!grid || !params) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "grid and params are required");
+  if (!(params->coll_check_time_increment > 0.0) || !(params->map_resolution >= 0.0) || !(grid->resolution > 0.0) ||
+      grid->nx < 1 || grid->ny < 1 || grid->nz < 1)
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT,
+                     "need coll_check_time_increment > 0, map_resolution >= 0, grid resolution > 0, grid dimensions >= 1");
+  if (batch == 0) return MTG_OK;
+  if (!vertex_values || !times || !cost_out || !grid->distance || (grad_out && !fixed_mask))
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT,
+                     "vertex_values, times, cost_out and grid->distance are required; grad_out needs fixed_mask");
+  if (mtg::collision_lds_bytes(N, K) > 64 * 1024)
+    return set_error(ctx, MTG_ERR_TOO_LARGE, "per-trajectory coefficients exceed LDS (reduce K)");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int V = K + 1, h = N / 2;
+  const size_t b_vals = sizeof(double) * (size_t)batch * V * h * D, b_mask = grad_out ? (size_t)batch * V : 0,
+               b_times = sizeof(double) * (size_t)batch * K,
+               b_grid = sizeof(float) * (size_t)grid->nx * grid->ny * grid->nz, b_cost = sizeof(double) * (size_t)batch,
+               b_grad = grad_out ? sizeof(double) * (size_t)batch * D * V * h : 0,
+               b_coll = collision_out ? (size_t)batch : 0, b_nev = n_evaluated_out ? sizeof(int32_t) * (size_t)batch : 0,
+               b_stat = status ? sizeof(int32_t) * (size_t)batch : 0;
+  const double *d_vals = vertex_values, *d_times = times;
+  const uint8_t* d_mask = fixed_mask;
+  const float* d_grid = grid->distance;
+  double *d_cost = cost_out, *d_grad = grad_out;
+  uint8_t* d_coll = collision_out;
+  int32_t *d_nev = n_evaluated_out, *d_stat = status;
+  const bool dev = flags & MTG_FLAG_DEVICE_PTRS;
+  char* base = nullptr;
+  size_t o_cost = 0, o_grad = 0, o_coll = 0, o_nev = 0, o_stat = 0;
+  if (!dev) {
+    size_t off = 0;
+    const size_t o_vals = off; off = align_up(off + b_vals);
+    const size_t o_mask = off; off = align_up(off + b_mask);
+    const size_t o_times = off; off = align_up(off + b_times);
+    const size_t o_grid = off; off = align_up(off + b_grid);
+    o_cost = off; off = align_up(off + b_cost);
+    o_grad = off; off = align_up(off + b_grad);
+    o_coll = off; off = align_up(off + b_coll);
+    o_nev = off; off = align_up(off + b_nev);
+    o_stat = off; off = align_up(off + b_stat);
+    MTG_HIP_TRY(ctx, ensure(&ctx->staging, &ctx->staging_bytes, std::max<size_t>(off, 256)));
+    base = static_cast<char*>(ctx->staging);
+    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_vals, vertex_values, b_vals, hipMemcpyHostToDevice, ctx->stream));
+    if (b_mask) MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_mask, fixed_mask, b_mask, hipMemcpyHostToDevice, ctx->stream));
+    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_times, times, b_times, hipMemcpyHostToDevice, ctx->stream));
+    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_grid, grid->distance, b_grid, hipMemcpyHostToDevice, ctx->stream));
+    d_vals = reinterpret_cast<const double*>(base + o_vals);
+    d_mask = b_mask ? reinterpret_cast<const uint8_t*>(base + o_mask) : nullptr;
+    d_times = reinterpret_cast<const double*>(base + o_times);
+    d_grid = reinterpret_cast<const float*>(base + o_grid);
+    d_cost = reinterpret_cast<double*>(base + o_cost);
+    d_grad = grad_out ? reinterpret_cast<double*>(base + o_grad) : nullptr;
+    d_coll = collision_out ? reinterpret_cast<uint8_t*>(base + o_coll) : nullptr;
+    d_nev = n_evaluated_out ? reinterpret_cast<int32_t*>(base + o_nev) : nullptr;
+    d_stat = status ? reinterpret_cast<int32_t*>(base + o_stat) : nullptr;
+  }
+  if (d_grad) MTG_HIP_TRY(ctx, hipMemsetAsync(d_grad, 0, b_grad, ctx->stream));
+  MTG_HIP_TRY(ctx, time_begin(ctx));
+  MTG_HIP_TRY(ctx, mtg::launch_collision_cost(N, d_vals, d_mask, d_times, *grid, d_grid, *params, d_cost, d_grad, d_coll,
+                                              d_nev, d_stat, batch, K, ctx->stream));
+  MTG_HIP_TRY(ctx, time_end(ctx));
+  if (!dev) {
+    MTG_HIP_TRY(ctx, hipMemcpyAsync(cost_out, base + o_cost, b_cost, hipMemcpyDeviceToHost, ctx->stream));
+    if (grad_out) MTG_HIP_TRY(ctx, hipMemcpyAsync(grad_out, base + o_grad, b_grad, hipMemcpyDeviceToHost, ctx->stream));
+    if (b_coll) MTG_HIP_TRY(ctx, hipMemcpyAsync(collision_out, base + o_coll, b_coll, hipMemcpyDeviceToHost, ctx->stream));
+    if (b_nev) MTG_HIP_TRY(ctx, hipMemcpyAsync(n_evaluated_out, base + o_nev, b_nev, hipMemcpyDeviceToHost, ctx->stream));
+    if (b_stat) MTG_HIP_TRY(ctx, hipMemcpyAsync(status, base + o_stat, b_stat, hipMemcpyDeviceToHost, ctx->stream));
+    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  } else if (!(flags & MTG_FLAG_ASYNC)) {
+    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return MTG_OK;
+}
+
 int mtg_time_jacobian_batch(mtg_ctx* ctx, int N, int D, int K, int derivative_to_optimize,
                             int64_t batch, const double* vertex_values, const double* times,
                             int n_candidates, const double* scales, double increment_time,

@@ -86,6 +86,14 @@ hipError_t launch_cost_at_times(int N, int r, const double* values, const uint8_
                                 const double* scales, double* cost, double* grad, int64_t B, int K, int D, int C,
                                 hipStream_t stream);
 
+// collision cost / gradient over a signed distance field (mtg_collision.hip); `distance` is the
+// device copy of grid.distance
+size_t collision_lds_bytes(int N, int K);
+hipError_t launch_collision_cost(int N, const double* values, const uint8_t* mask, const double* times,
+                                 const mtg_sdf_grid& grid, const float* distance, const mtg_collision_params& p,
+                                 double* cost, double* grad, uint8_t* collision, int32_t* n_evaluated, int32_t* status,
+                                 int64_t B, int K, hipStream_t stream);
+
 // segment-time cost sweep + time Jacobian on the matrix cores (mtg_jacobian.hip)
 size_t time_jacobian_lds_bytes(int N, int D, int K, int C);
 hipError_t launch_time_jacobian(int N, int r, const double* values, const double* times, const double* scales,

@@ -255,6 +255,50 @@ class Context:
                   self.handle)
         return (cost, g) if grad else cost
 
+    def collision_cost_batch(self, N, vertex_values, times, grid, params, mask=None, grad=False, asynchronous=False):
+        """getCostAndGradientCollision for a batch (include/mtg.h mtg_collision_cost_batch): vertex_values
+        [B][V][h][3] (all derivatives), times [B][K], grid an SdfGrid, params a CollisionParams.  numpy
+        arrays (staged, the grid included) or torch CUDA tensors (then grid.distance is one too, the
+        launch goes to torch's current stream and asynchronous=True does not wait for it).  Returns
+        dict(cost [B], collision [B] uint8, n_evaluated [B] int32, status [B] int32) and, with grad=True
+        (needs mask), grad [B][3][V*h] packed as cost_at_times_batch's."""
+        dev = _is_torch(vertex_values) and vertex_values.is_cuda
+        B, V, h, D = vertex_values.shape
+        K = V - 1
+        assert h == N // 2 and tuple(times.shape) == (B, K)
+        assert not grad or mask is not None, "grad needs mask"
+        if dev:
+            import torch
+            assert _is_torch(grid.distance) and grid.distance.is_cuda, "device call: grid.distance must be a CUDA tensor"
+            kw = dict(device=vertex_values.device)
+            out = {"cost": torch.empty(B, dtype=torch.float64, **kw),
+                   "collision": torch.empty(B, dtype=torch.uint8, **kw),
+                   "n_evaluated": torch.empty(B, dtype=torch.int32, **kw),
+                   "status": torch.empty(B, dtype=torch.int32, **kw)}
+            if grad:
+                out["grad"] = torch.empty((B, D, V * h), dtype=torch.float64, **kw)
+            flags = nat.MTG_FLAG_DEVICE_PTRS | (nat.MTG_FLAG_ASYNC if asynchronous else 0)
+            self.set_stream(torch.cuda.current_stream(vertex_values.device).cuda_stream)
+        else:
+            vertex_values = np.ascontiguousarray(vertex_values, dtype=np.float64)
+            times = np.ascontiguousarray(times, dtype=np.float64)
+            mask = np.ascontiguousarray(mask, dtype=np.uint8) if mask is not None else None
+            out = {"cost": np.empty(B), "collision": np.empty(B, np.uint8), "n_evaluated": np.empty(B, np.int32),
+                   "status": np.empty(B, np.int32)}
+            if grad:
+                out["grad"] = np.zeros((B, D, V * h))
+            flags = 0
+            self.reset_stream()
+        g, keep = grid.native()
+        nat.check(self._lib.mtg_collision_cost_batch(self.handle, N, D, K, B, _addr(vertex_values),
+                                                     _addr(mask) if grad else None, _addr(times), ctypes.byref(g),
+                                                     ctypes.byref(params.native()), _addr(out["cost"]),
+                                                     _addr(out.get("grad")), _addr(out["collision"]),
+                                                     _addr(out["n_evaluated"]), _addr(out["status"]), flags),
+                  self.handle)
+        del keep
+        return out
+
     def time_jacobian_batch(self, N, r, vertex_values, times, scales, increment_time=0.0, jacobian=True):
         """Cost sweep + segment-time Jacobian on the matrix cores (include/mtg.h mtg_time_jacobian_batch):
         cost [B][C] = sum_dims d^T R(T_c) d and jac [B][C][K] = dJ/dT_i at T_c (exact for
@@ -457,6 +501,10 @@ def solve_linear_batch(N, r, values, mask, times, device=0, **kw):
     return default_context(device).solve_linear_batch(N, r, values, mask, times, **kw)
 
 
+def collision_cost_batch(N, vertex_values, times, grid, params, device=0, **kw):
+    return default_context(device).collision_cost_batch(N, vertex_values, times, grid, params, **kw)
+
+
 def shard_range(batch, n_shards, shard):
     """[begin, end) of contiguous shard `shard` of `n_shards` (mtg_shard_range)."""
     b, e = ctypes.c_int64(0), ctypes.c_int64(0)
@@ -491,6 +539,77 @@ def solve_linear_batch_multi(contexts, N, r, values, mask, times, free=False, n_
                                           _addr(out.get("free")), _addr(out.get("n_free")), _addr(out.get("cost")),
                                           _addr(out.get("status")), 0)
     nat.check(rc, contexts[0].handle)
+    return out
+
+
+class SdfGrid:
+    """struct mtg_sdf_grid (include/mtg.h): a dense signed distance field, distance [nx][ny][nz] float32
+    (numpy, or a torch CUDA tensor for device calls), origin = the low corner of cell (0, 0, 0),
+    resolution = the cell edge, oob_distance = the value outside the grid."""
+
+    def __init__(self, distance, origin, resolution, oob_distance=0.0):
+        if not _is_torch(distance):
+            distance = np.ascontiguousarray(distance, dtype=np.float32)
+        else:
+            import torch
+            assert distance.dtype == torch.float32 and distance.is_contiguous()
+        assert len(distance.shape) == 3
+        self.distance = distance
+        self.origin = tuple(float(x) for x in origin)
+        self.resolution = float(resolution)
+        self.oob_distance = float(oob_distance)
+
+    def native(self):
+        """(the ctypes struct, the array it points into: keep it alive for the call)"""
+        nx, ny, nz = (int(n) for n in self.distance.shape)
+        g = nat.SdfGrid(_addr(self.distance), nx, ny, nz, (ctypes.c_double * 3)(*self.origin), self.resolution,
+                        self.oob_distance)
+        return g, self.distance
+
+
+class CollisionParams:
+    """struct mtg_collision_params (include/mtg.h), the reference's optimization_parameters_ fields of the
+    collision term: dt = coll_check_time_increment; map_resolution is the arc-length gate, the bounds
+    margin and the finite-difference increment."""
+
+    def __init__(self, dt, map_resolution, epsilon, robot_radius, coll_pot_multiplier=1.0, min_bound=(0.0, 0.0, 0.0),
+                 max_bound=(0.0, 0.0, 0.0), use_continuous_distance=False):
+        self.dt = float(dt)
+        self.map_resolution = float(map_resolution)
+        self.epsilon = float(epsilon)
+        self.robot_radius = float(robot_radius)
+        self.coll_pot_multiplier = float(coll_pot_multiplier)
+        self.min_bound = tuple(float(x) for x in min_bound)
+        self.max_bound = tuple(float(x) for x in max_bound)
+        self.use_continuous_distance = bool(use_continuous_distance)
+
+    def native(self):
+        return nat.CollisionParams(self.dt, self.map_resolution, self.epsilon, self.robot_radius,
+                                   self.coll_pot_multiplier, (ctypes.c_double * 3)(*self.min_bound),
+                                   (ctypes.c_double * 3)(*self.max_bound), int(self.use_continuous_distance), 0)
+
+
+def host_collision_cost_batch(N, vertex_values, times, grid, params, mask=None, grad=False, threads=1):
+    """The library's host path of Context.collision_cost_batch (mtg_host_collision_cost_batch): the
+    reference's loop in scalar C++, no GPU.  Same arguments (numpy arrays) and outputs."""
+    lib = nat.load()
+    vertex_values = np.ascontiguousarray(vertex_values, dtype=np.float64)
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    B, V, h, D = vertex_values.shape
+    K = V - 1
+    assert h == N // 2 and times.shape == (B, K)
+    assert not grad or mask is not None, "grad needs mask"
+    mask = np.ascontiguousarray(mask, dtype=np.uint8) if mask is not None else None
+    out = {"cost": np.empty(B), "collision": np.empty(B, np.uint8), "n_evaluated": np.empty(B, np.int32),
+           "status": np.empty(B, np.int32)}
+    if grad:
+        out["grad"] = np.zeros((B, D, V * h))
+    g, keep = grid.native()
+    nat.check(lib.mtg_host_collision_cost_batch(N, D, K, B, _addr(vertex_values), _addr(mask) if grad else None,
+                                                _addr(times), ctypes.byref(g), ctypes.byref(params.native()),
+                                                _addr(out["cost"]), _addr(out.get("grad")), _addr(out["collision"]),
+                                                _addr(out["n_evaluated"]), _addr(out["status"]), threads))
+    del keep
     return out
 
 
