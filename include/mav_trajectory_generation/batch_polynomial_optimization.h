@@ -155,6 +155,15 @@ class BatchPolynomialOptimization {
                                    is_collision, n_evaluated, status, flags),
           ctx_, "mtg_collision_cost_batch");
   }
+  // soft-constraint cost of the magnitude limits (and gradient, packed as costAtTimes' grad)
+  // (mtg_soft_constraint_cost_batch: getCostAndGradientSoftConstraints, nl_impl:2025-2091); D <= 4
+  void softConstraintCost(int64_t batch, const double* vertex_values, const uint8_t* mask, const double* times,
+                          const mtg_soft_constraint_params& params, double* cost, double* grad = nullptr,
+                          mtg_extremum* maxima = nullptr, int32_t* status = nullptr, unsigned flags = 0) {
+    check(mtg_soft_constraint_cost_batch(ctx_, N, D_, K_, batch, vertex_values, mask, times, &params, cost, grad,
+                                         maxima, status, flags),
+          ctx_, "mtg_soft_constraint_cost_batch");
+  }
   void coefficientsFromVertices(int64_t batch, const double* vertex_values, const double* times, double* coeffs,
                                 unsigned flags = 0) {
     check(mtg_coefficients_from_vertices_batch(ctx_, N, D_, K_, batch, vertex_values, times, coeffs, flags), ctx_,
@@ -211,6 +220,26 @@ inline void collisionCost(int K, int64_t batch, const double* vertex_values, con
     check(mtg_host_collision_cost_batch(N, 3, K, batch, vertex_values, mask, times, &grid, &params, cost, grad,
                                         is_collision, n_evaluated, status, 1),
           nullptr, "mtg_host_collision_cost_batch");
+  }
+}
+
+// getCostAndGradientSoftConstraints for trajectories of N coefficients, K segments and D dimensions,
+// without a BatchPolynomialOptimization object: on the library's host path
+// (mtg_host_soft_constraint_cost_batch) unless the execution policy is kDevice, as collisionCost.
+// Host pointers.
+template <int N>
+inline void softConstraintCost(int D, int K, int64_t batch, const double* vertex_values, const uint8_t* mask,
+                               const double* times, const mtg_soft_constraint_params& params, double* cost,
+                               double* grad = nullptr, mtg_extremum* maxima = nullptr, int32_t* status = nullptr) {
+  if (singleOnDevice()) {
+    mtg_ctx* ctx = defaultContext();
+    check(mtg_soft_constraint_cost_batch(ctx, N, D, K, batch, vertex_values, mask, times, &params, cost, grad, maxima,
+                                         status, 0),
+          ctx, "mtg_soft_constraint_cost_batch");
+  } else {
+    check(mtg_host_soft_constraint_cost_batch(N, D, K, batch, vertex_values, mask, times, &params, cost, grad, maxima,
+                                              status, 1),
+          nullptr, "mtg_host_soft_constraint_cost_batch");
   }
 }
 

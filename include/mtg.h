@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define MTG_ABI_VERSION 1
+#define MTG_ABI_VERSION 2   /* 2: + mtg_soft_constraint_cost_batch, mtg_host_soft_constraint_cost_batch */
 
 /* Call-level return codes. */
 #define MTG_OK 0
@@ -240,7 +240,8 @@ int mtg_cost_at_times_batch(mtg_ctx* ctx, int N, int D, int K, int derivative_to
  * matrix-core path).  Replaces, per trajectory b and candidate allocation c,
  *   updateSegmentTimes(T_c) + getCostAndGradientDerivative(NULL)      nl_impl:1452-1520
  * and the J_d part of getCostAndGradientTime's per-segment gradient    nl_impl:2153-2238
- * (dJd_dt; the collision, soft-constraint and w_* weighting terms are not part of this path):
+ * (dJd_dt; the collision, soft-constraint and w_* weighting terms are not part of this path; J_c is
+ * mtg_collision_cost_batch and J_sc is mtg_soft_constraint_cost_batch):
  *   cost_out[b][c]      = sum_dims d^T R(T_c) d                 (as mtg_cost_at_times_batch)
  *   jac_out[b][c][i]    = dJ/dT_i at T_c                        (nullable)
  * with T_c[i] = times[b][i] * scales[c][i] and d = vertex_values[b] (ALL derivatives of every
@@ -371,6 +372,65 @@ int mtg_host_collision_cost_batch(int N, int D, int K, int64_t batch, const doub
                                   const uint8_t* fixed_mask, const double* times, const mtg_sdf_grid* grid,
                                   const mtg_collision_params* params, double* cost_out, double* grad_out,
                                   uint8_t* collision_out, int32_t* n_evaluated_out, int32_t* status, int threads);
+
+/* ---- Soft-constraint term of the nonlinear objective (use_soft_constraints, the reference's default,
+ * polynomial_optimization_nonlinear.h:57): the magnitude limits added with
+ * addMaximumMagnitudeConstraint, as a cost. */
+typedef struct mtg_soft_constraint_params {
+  int32_t n_constraints;      /* 1 .. 8 (inequality_constraints_, addMaximumMagnitudeConstraint) */
+  int32_t derivative[8];      /* 0 .. min(4, N-2): POSITION .. SNAP, the reference's switch nl_impl:2356-2386 */
+  double  limit[8];           /* ConstraintData::value, > 0 */
+  double  weight;             /* soft_constraint_weight (reference default 100) */
+  double  maximum_cost;       /* reference default 1e12 */
+  double  increment;          /* the reference's map_resolution: finite-difference step */
+} mtg_soft_constraint_params;
+
+/* Batched getCostAndGradientSoftConstraints (nl_impl:2025-2091) with
+ * evaluateMaximumMagnitudeAsSoftConstraint (:2396-2425) and
+ * PolynomialOptimization::computeMaximumOfMagnitude (lin_impl:470-503), restated.  1 <= D <= 4, N one
+ * of 6, 8, 10, 12, K >= 1 up to the LDS limit below.  Per trajectory:
+ *   cost = sum_c min(maximum_cost, exp(weight * (max_c - limit_c) / limit_c))    (in constraint order)
+ *   max_c = computeMaximumOfMagnitude<derivative_c>: the candidates are, per segment in order, t = 0
+ *     and then the real roots in [0, T_i] of sum_d conv(p_d^(k), p_d^(k+1)) (D = 1: of p^(k+1)), and
+ *     after the last segment t = T_K.  A candidate replaces the best so far only when strictly larger
+ *     (the first one wins ties).  Interior segment ends are NOT candidates -- the difference from
+ *     Trajectory::computeMinMaxMagnitude / mtg_min_max_magnitude_batch.  Roots are isolated and refined
+ *     exactly as there (256 samples per segment, safeguarded Newton).
+ *   grad[d][n] = (cost(x + increment e_{d,n}) - cost(x - increment e_{d,n})) / (2 increment) for
+ *     dimension d and free index n (the reference's central difference, left side evaluated first);
+ *     increment == 0 divides 0 by 0, as in the reference (a NaN gradient, a finite cost).
+ * vertex_values [B][V][h][D] holds ALL derivatives; the coefficients are formed from them as
+ * mtg_coefficients_from_vertices_batch does.  fixed_mask [B][V] is needed only for grad_out.
+ * cost_out [B]; grad_out [B][D][V*h] (nullable; free derivatives in the reference's (vertex,
+ * derivative) order, entries >= n_free are 0: the packing of mtg_cost_at_times_batch and
+ * mtg_collision_cost_batch, so the three terms add); maxima_out [B][n_constraints] (nullable): the
+ * unperturbed trajectory's optimization_info_.maxima; status [B] (nullable).  grad_out == NULL skips
+ * the gradient and leaves the cost's bits unchanged.  A trajectory with a T_i that is not positive and
+ * finite gets MTG_TRAJ_BAD_TIME, a NaN cost (and NaN maxima) and a zero gradient.
+ * MTG_ERR_INVALID_ARGUMENT: D outside 1..4; N not in {6, 8, 10, 12}; n_constraints outside 1..8; a
+ * derivative outside 0..min(4, N-2) or a limit that is not > 0 (a deviation: the reference returns a
+ * zero violation for a derivative its switch does not know).  params is a host struct, read during
+ * the call.  Results do not depend on the trajectory's place in the batch or on the batch.
+ * MTG_ERR_TOO_LARGE: the device call keeps one trajectory (vertex values, coefficients, per-segment
+ * maxima) and at least eight search areas in 64 KiB of LDS, which bounds K -- with two constraints
+ * K <= 189 (N = 6), 148 (8), 120 (10), 100 (12) at D = 3; 92 at N = 10, D = 4; 264 at N = 10, D = 1;
+ * eight constraints: K <= 79 at N = 10, D = 3 -- unlike mtg_min_max_magnitude_batch, which streams
+ * segments and takes K <= 256.  The host path has no such limit.
+ * Not covered: the soft-constraint part of getCostAndGradientTime (nl_impl:2199-2226).  As read,
+ * updateSegmentTimes does not rebuild segments_, so the reference's dJsc_dt differences two equal
+ * numbers; no semantics is invented for it here. */
+int mtg_soft_constraint_cost_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* vertex_values,
+                                   const uint8_t* fixed_mask, const double* times,
+                                   const mtg_soft_constraint_params* params, double* cost_out, double* grad_out,
+                                   mtg_extremum* maxima_out, int32_t* status, unsigned flags);
+
+/* Host (CPU) path of mtg_soft_constraint_cost_batch, no context and no GPU needed: the reference's
+ * loop written literally -- for every (dimension, free index, side) ALL coefficients are re-formed and
+ * ALL segments searched.  All host pointers; threads <= 0: mtg_host_default_threads(). */
+int mtg_host_soft_constraint_cost_batch(int N, int D, int K, int64_t batch, const double* vertex_values,
+                                        const uint8_t* fixed_mask, const double* times,
+                                        const mtg_soft_constraint_params* params, double* cost_out,
+                                        double* grad_out, mtg_extremum* maxima_out, int32_t* status, int threads);
 
 /* Timing of the most recent kernel launch(es) of this context on its stream
  * (hipEvent pair around the solve kernel), in milliseconds. */

@@ -62,6 +62,12 @@ class CollisionParams(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class SoftConstraintParams(ctypes.Structure):
+    """struct mtg_soft_constraint_params (include/mtg.h)."""
+    _fields_ = [("n_constraints", ctypes.c_int32), ("derivative", ctypes.c_int32 * 8), ("limit", ctypes.c_double * 8),
+                ("weight", ctypes.c_double), ("maximum_cost", ctypes.c_double), ("increment", ctypes.c_double)]
+
+
 _SIGNATURES = {
     "mtg_abi_version": (ctypes.c_int, []),
     "mtg_solve_kernel": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint]),
@@ -107,6 +113,13 @@ _SIGNATURES = {
                                                      _c_dp, _c_dp, ctypes.POINTER(SdfGrid),
                                                      ctypes.POINTER(CollisionParams), _c_dp, _c_dp, _c_dp, _c_dp,
                                                      _c_dp, ctypes.c_int]),
+    "mtg_soft_constraint_cost_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.c_int64, _c_dp, _c_dp, _c_dp,
+                                                      ctypes.POINTER(SoftConstraintParams), _c_dp, _c_dp, _c_dp, _c_dp,
+                                                      ctypes.c_uint]),
+    "mtg_host_soft_constraint_cost_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                           _c_dp, _c_dp, _c_dp, ctypes.POINTER(SoftConstraintParams),
+                                                           _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mtg_time_jacobian_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_int64, _c_dp, _c_dp, ctypes.c_int, _c_dp,
                                                ctypes.c_double, _c_dp, _c_dp, ctypes.c_uint]),

@@ -1017,6 +1017,80 @@ int mtg_collision_cost_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, c
   return MTG_OK;
 }
 
+int mtg_soft_constraint_cost_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* vertex_values,
+                                   const uint8_t* fixed_mask, const double* times,
+                                   const mtg_soft_constraint_params* params, double* cost_out, double* grad_out,
+                                   mtg_extremum* maxima_out, int32_t* status, unsigned flags) {
+  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
+  if (N < 6 || N > 12 || (N % 2)) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "N must be 6, 8, 10 or 12");
+  if (D < 1 || D > 4) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "the soft-constraint term needs 1 <= D <= 4");
+  if (K < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need K >= 1, batch >= 0");
+  if (!params || params->n_constraints < 1 || params->n_constraints > 8)
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "params with 1 <= n_constraints <= 8 are required");
+  const int C = params->n_constraints, kmax = N - 2 < 4 ? N - 2 : 4;
+  for (int c = 0; c < C; ++c)
+    if (params->derivative[c] < 0 || params->derivative[c] > kmax || !(params->limit[c] > 0.0))
+      return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "need 0 <= derivative <= min(4, N - 2) and limit > 0");
+  if (batch == 0) return MTG_OK;
+  if (!vertex_values || !times || !cost_out || (grad_out && !fixed_mask))
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT,
+                     "vertex_values, times and cost_out are required; grad_out needs fixed_mask");
+  if (mtg::soft_constraint_threads(N, D, K, C) == 0 || batch > 0x7fffffff)
+    return set_error(ctx, MTG_ERR_TOO_LARGE, "per-trajectory working set exceeds LDS (reduce K), or batch >= 2^31");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int V = K + 1, h = N / 2;
+  const size_t b_vals = sizeof(double) * (size_t)batch * V * h * D, b_mask = grad_out ? (size_t)batch * V : 0,
+               b_times = sizeof(double) * (size_t)batch * K, b_cost = sizeof(double) * (size_t)batch,
+               b_grad = grad_out ? sizeof(double) * (size_t)batch * D * V * h : 0,
+               b_max = maxima_out ? sizeof(mtg_extremum) * (size_t)batch * C : 0,
+               b_stat = status ? sizeof(int32_t) * (size_t)batch : 0;
+  const double *d_vals = vertex_values, *d_times = times;
+  const uint8_t* d_mask = fixed_mask;
+  double *d_cost = cost_out, *d_grad = grad_out;
+  mtg_extremum* d_max = maxima_out;
+  int32_t* d_stat = status;
+  const bool dev = flags & MTG_FLAG_DEVICE_PTRS;
+  char* base = nullptr;
+  size_t o_cost = 0, o_grad = 0, o_max = 0, o_stat = 0;
+  if (!dev) {
+    size_t off = 0;
+    const size_t o_vals = off; off = align_up(off + b_vals);
+    const size_t o_mask = off; off = align_up(off + b_mask);
+    const size_t o_times = off; off = align_up(off + b_times);
+    o_cost = off; off = align_up(off + b_cost);
+    o_grad = off; off = align_up(off + b_grad);
+    o_max = off; off = align_up(off + b_max);
+    o_stat = off; off = align_up(off + b_stat);
+    MTG_HIP_TRY(ctx, ensure(&ctx->staging, &ctx->staging_bytes, std::max<size_t>(off, 256)));
+    base = static_cast<char*>(ctx->staging);
+    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_vals, vertex_values, b_vals, hipMemcpyHostToDevice, ctx->stream));
+    if (b_mask) MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_mask, fixed_mask, b_mask, hipMemcpyHostToDevice, ctx->stream));
+    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_times, times, b_times, hipMemcpyHostToDevice, ctx->stream));
+    d_vals = reinterpret_cast<const double*>(base + o_vals);
+    d_mask = b_mask ? reinterpret_cast<const uint8_t*>(base + o_mask) : nullptr;
+    d_times = reinterpret_cast<const double*>(base + o_times);
+    d_cost = reinterpret_cast<double*>(base + o_cost);
+    d_grad = grad_out ? reinterpret_cast<double*>(base + o_grad) : nullptr;
+    d_max = maxima_out ? reinterpret_cast<mtg_extremum*>(base + o_max) : nullptr;
+    d_stat = status ? reinterpret_cast<int32_t*>(base + o_stat) : nullptr;
+  }
+  MTG_HIP_TRY(ctx, time_begin(ctx));  // (the kernel writes every entry of grad_out itself)
+  MTG_HIP_TRY(ctx, mtg::launch_soft_constraint_cost(N, d_vals, d_mask, d_times, *params, d_cost, d_grad, d_max, d_stat,
+                                                    batch, K, D, ctx->stream));
+  MTG_HIP_TRY(ctx, time_end(ctx));
+  if (!dev) {
+    MTG_HIP_TRY(ctx, hipMemcpyAsync(cost_out, base + o_cost, b_cost, hipMemcpyDeviceToHost, ctx->stream));
+    if (grad_out) MTG_HIP_TRY(ctx, hipMemcpyAsync(grad_out, base + o_grad, b_grad, hipMemcpyDeviceToHost, ctx->stream));
+    if (b_max) MTG_HIP_TRY(ctx, hipMemcpyAsync(maxima_out, base + o_max, b_max, hipMemcpyDeviceToHost, ctx->stream));
+    if (b_stat) MTG_HIP_TRY(ctx, hipMemcpyAsync(status, base + o_stat, b_stat, hipMemcpyDeviceToHost, ctx->stream));
+    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  } else if (!(flags & MTG_FLAG_ASYNC)) {
+    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return MTG_OK;
+}
+
 int mtg_time_jacobian_batch(mtg_ctx* ctx, int N, int D, int K, int derivative_to_optimize,
                             int64_t batch, const double* vertex_values, const double* times,
                             int n_candidates, const double* scales, double increment_time,

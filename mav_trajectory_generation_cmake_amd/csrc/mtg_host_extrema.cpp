@@ -1,7 +1,8 @@
 // mtg_host_extrema.cpp -- host (CPU) path of mtg_min_max_magnitude_batch:
 // mtg_host_min_max_magnitude_batch, the reference's Trajectory::computeMinMaxMagnitude
 // (src/trajectory.cpp:181-218) for the drop-in's single trajectories, which the reference also
-// computes on the CPU.  Same algorithm as the HIP kernel (mtg_extrema.hip): per segment the
+// computes on the CPU.  Same algorithm as the HIP kernel (mtg_extrema.hip; the segment search is
+// mtg_host_extrema_common.h, shared with mtg_host_soft_constraint.cpp): per segment the
 // candidates t = 0, t = T and the real roots in [0, T] of sum_d conv(p_d^(k), p_d^(k+1)) (one
 // dimension: of p^(k+1)), isolated by sign changes on 256 uniform samples and refined by safeguarded
 // Newton-bisection; the magnitude at each candidate; the first candidate / segment wins ties.
@@ -12,109 +13,21 @@
 #include <vector>
 
 #include "mtg.h"
+#include "mtg_host_extrema_common.h"
 #include "mtg_host_threads.h"
 
 namespace {
 
-constexpr int kSamples = 256;
-
-double ff(int j, int n) {  // falling factorial j! / (j - n)!
-  double f = 1.0;
-  for (int q = 0; q < n; ++q) f *= (double)(j - q);
-  return f;
-}
-
-double horner(const double* c, int len, double t) {
-  double acc = 0.0;
-  for (int j = len - 1; j >= 0; --j) acc = acc * t + c[j];
-  return acc;
-}
-
-struct Ext {
-  double t, v;
-};
-
 // one trajectory: coeffs [K][D][N], times [K]
 void one(int N, int D, int K, const double* coeffs, const double* times, int k, unsigned dims, mtg_extremum* out_min,
          mtg_extremum* out_max) {
-  const int nd = N - k, ndd = N - k - 1;
-  const int ndim = __builtin_popcount(dims);
-  Ext m{0.0, DBL_MAX}, M{0.0, -DBL_MAX};
+  mtg::HostExt m{0.0, DBL_MAX}, M{0.0, -DBL_MAX};
   int im = 0, iM = 0;
   std::vector<double> f(2 * N), q(N), q1(N);
   for (int i = 0; i < K; ++i) {
-    const double T = times[i];
-    const double* cs = coeffs + (size_t)i * D * N;
-    for (double& x : f) x = 0.0;
-    int lf = 0;
-    for (int d = 0; d < D; ++d) {
-      if (!((dims >> d) & 1u)) continue;
-      for (int j = 0; j < N; ++j) {
-        q[j] = j < nd ? cs[d * N + j + k] * ff(j + k, k) : 0.0;
-        q1[j] = j < ndd ? cs[d * N + j + k + 1] * ff(j + k + 1, k + 1) : 0.0;
-      }
-      if (ndim == 1) {  // one dimension: the roots of p^(k+1) (segment.cpp:124-130)
-        for (int j = 0; j < ndd; ++j) f[j] = q1[j];
-        lf = ndd;
-      } else {  // convolve(d, dd) summed over the dimensions
-        for (int a = 0; a < nd; ++a)
-          for (int c = 0; c < ndd; ++c) f[a + c] += q[a] * q1[c];
-        lf = nd + ndd - 1;
-      }
-    }
-    auto mag = [&](double t) {
-      double s = 0.0;
-      for (int d = 0; d < D; ++d) {
-        if (!((dims >> d) & 1u)) continue;
-        double acc = 0.0;
-        for (int j = nd - 1; j >= 0; --j) acc = acc * t + cs[d * N + j + k] * ff(j + k, k);
-        s += acc * acc;
-      }
-      return std::sqrt(s);
-    };
-    Ext lo{0.0, DBL_MAX}, hi{0.0, -DBL_MAX};
-    auto consider = [&](double t) {
-      const double v = mag(t);
-      if (v > hi.v) hi = Ext{t, v};
-      if (v < lo.v) lo = Ext{t, v};
-    };
-    consider(0.0);  // t_start, t_end first (polynomial.cpp:38-39), then the roots in order
-    consider(T);
-    const double h = T / kSamples;
-    double ta = 0.0, fa = horner(f.data(), lf, 0.0);
-    if (fa == 0.0) consider(0.0);
-    for (int s = 1; s <= kSamples; ++s) {
-      const double tb = s == kSamples ? T : s * h;
-      const double fb = horner(f.data(), lf, tb);
-      if (fb == 0.0) {
-        consider(tb);
-      } else if ((fa < 0.0 && fb > 0.0) || (fa > 0.0 && fb < 0.0)) {
-        double a0 = ta, b0 = tb, fa0 = fa, x = ta - fa * ((tb - ta) / (fb - fa));  // from the secant point
-        if (!(x > ta && x < tb)) x = 0.5 * (ta + tb);
-        for (int it = 0; it < 60; ++it) {
-          double fx = 0.0, dfx = 0.0, ga = 0.0;  // f and f' in one Horner pass; ga: f(x)'s error scale
-          const double ax = std::fabs(x);
-          for (int j = lf - 1; j >= 0; --j) {
-            dfx = dfx * x + fx;
-            fx = fx * x + f[j];
-            ga = ga * ax + std::fabs(f[j]);
-          }
-          if (std::fabs(fx) <= (2.0 * (2 * N - 2) * DBL_EPSILON) * ga) break;  // within rounding of 0
-          if ((fx < 0.0) == (fa0 < 0.0)) a0 = x, fa0 = fx;
-          else b0 = x;
-          double xn = x - fx / dfx;
-          if (!(xn > a0 && xn < b0)) xn = 0.5 * (a0 + b0);
-          if (b0 - a0 <= 4.0 * DBL_EPSILON * std::fmax(std::fabs(a0), std::fabs(b0)) || xn == x) {
-            x = xn;
-            break;
-          }
-          x = xn;
-        }
-        consider(x);
-      }
-      ta = tb;
-      fa = fb;
-    }
+    mtg::HostExt lo, hi;
+    mtg::host_segment_extrema(N, D, coeffs + (size_t)i * D * N, times[i], k, dims, mtg::SegmentCandidates::kBothEnds,
+                              f.data(), q.data(), q1.data(), &lo, &hi);
     if (i == 0 || lo.v < m.v) m = lo, im = i;  // strict: the first segment wins ties
     if (i == 0 || hi.v > M.v) M = hi, iM = i;
   }

@@ -94,6 +94,15 @@ hipError_t launch_collision_cost(int N, const double* values, const uint8_t* mas
                                  double* cost, double* grad, uint8_t* collision, int32_t* n_evaluated, int32_t* status,
                                  int64_t B, int K, hipStream_t stream);
 
+// soft-constraint cost / gradient of the magnitude limits (mtg_soft_constraint.hip): threads per block
+// for a shape (0: the trajectory's working set exceeds LDS) and the block's LDS bytes
+int soft_constraint_threads(int N, int D, int K, int C);
+size_t soft_constraint_lds_bytes(int N, int D, int K, int C, int threads);
+hipError_t launch_soft_constraint_cost(int N, const double* values, const uint8_t* mask, const double* times,
+                                       const mtg_soft_constraint_params& params, double* cost, double* grad,
+                                       mtg_extremum* maxima, int32_t* status, int64_t B, int K, int D,
+                                       hipStream_t stream);
+
 // segment-time cost sweep + time Jacobian on the matrix cores (mtg_jacobian.hip)
 size_t time_jacobian_lds_bytes(int N, int D, int K, int C);
 hipError_t launch_time_jacobian(int N, int r, const double* values, const double* times, const double* scales,

@@ -7,7 +7,8 @@
 //   (fixed and free) is given, nothing is solved.  Same arithmetic as the solve kernels'
 //   epilogue: A(T)^-1 = diag(T^-j) A(1)^-1 S(T) from the exact-rational A(1)^-1 table, with the
 //   segment's start position subtracted first (only c_0 changes; no cancellation of p_i
-//   against p_{i+1} in c_j, j >= h).
+//   against p_{i+1} in c_j, j >= h).  The per-(segment, dimension) part is mtg_vertex_common.h,
+//   shared with mtg_soft_constraint.hip.
 // * vertex_derivatives: the reference's M^+ A p (nl_impl:162-180, used by
 //   computeInitialSolutionWithoutPositionConstraints): the end derivatives A_i c_i of every
 //   segment, mapped to the (vertex, derivative) unknowns by the pseudo-inverse of the 0/1
@@ -17,7 +18,7 @@
 // Both are HBM-bound streams.  A block of 256 threads owns TB consecutive trajectories: it
 // stages their input (contiguous in HBM) into LDS with coalesced loads, computes one item per
 // thread out of LDS, writes the results into LDS and stores them as one contiguous run.
-#include "mtg_device.h"
+#include "mtg_vertex_common.h"
 
 namespace mtg {
 
@@ -68,40 +69,11 @@ __global__ __launch_bounds__(kVtxThreads) void coefficients_from_vertices_kernel
   stage_copy<8>(values + b0 * xsz, xv, nb * xsz, tid);
   stage_copy<2>(times + b0 * K, tl, nb * K, tid);
   __syncthreads();
-  const double* Ai1 = c_a1inv + MTG_A1INV_OFF(N);
   for (int it = tid; it < nb * K * D; it += kVtxThreads) {
     const int bl = it / (K * D), rem = it - bl * (K * D), i = rem / D, d = rem - i * D;
     const double T = tl[bl * K + i];
     const double* x = xv + bl * xsz;
-    double s[H];
-    s[0] = 1.0;
-#pragma unroll
-    for (int k = 1; k < H; ++k) s[k] = s[k - 1] * T;
-    double sh[N];
-#pragma unroll
-    for (int k = 0; k < H; ++k) {
-      sh[k] = s[k] * x[(i * H + k) * D + d];
-      sh[H + k] = s[k] * x[((i + 1) * H + k) * D + d];
-    }
-    const double p0 = sh[0];
-    sh[0] = 0.0;
-    sh[H] -= p0;
-    const double tinv = rcp(T);
-    double tp = 1.0;
-    double* out = co + (size_t)it * N;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      double acc;
-      if (j < H) {
-        acc = (j == 0) ? p0 : Ai1[j * N + j] * sh[j];
-      } else {
-        acc = 0.0;
-#pragma unroll
-        for (int q = 1; q < N; ++q) acc += Ai1[j * N + q] * sh[q];
-      }
-      out[j] = acc * tp;
-      tp *= tinv;
-    }
+    coefficients_from_ends<N>([&](int e, int k) { return x[((i + e) * H + k) * D + d]; }, T, co + (size_t)it * N);
   }
   __syncthreads();
   double* dst = coeffs + b0 * csz;

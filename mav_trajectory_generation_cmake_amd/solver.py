@@ -299,6 +299,46 @@ class Context:
         del keep
         return out
 
+    def soft_constraint_cost_batch(self, N, vertex_values, times, params, mask=None, grad=False, asynchronous=False):
+        """getCostAndGradientSoftConstraints for a batch (include/mtg.h mtg_soft_constraint_cost_batch):
+        vertex_values [B][V][h][D] (all derivatives), times [B][K], params a SoftConstraintParams.  numpy
+        arrays (staged) or torch CUDA tensors (the launch then goes to torch's current stream and
+        asynchronous=True does not wait for it).  Returns dict(cost [B], grad, maxima [B][C], status [B]
+        int32): grad is None unless grad=True (needs mask), then [B][D][V*h] packed as
+        cost_at_times_batch's; maxima is a structured array (time, value, segment) for numpy input and
+        for torch input a float64 tensor [B][C][3] holding the same 24-byte records
+        (.cpu().numpy().view(EXTREMUM_DTYPE)[..., 0] decodes it)."""
+        dev = _is_torch(vertex_values) and vertex_values.is_cuda
+        B, V, h, D = vertex_values.shape
+        K = V - 1
+        assert h == N // 2 and tuple(times.shape) == (B, K)
+        assert not grad or mask is not None, "grad needs mask"
+        p = params.native()
+        C = max(int(p.n_constraints), 1)
+        if dev:
+            import torch
+            kw = dict(device=vertex_values.device)
+            out = {"cost": torch.empty(B, dtype=torch.float64, **kw),
+                   "grad": torch.empty((B, D, V * h), dtype=torch.float64, **kw) if grad else None,
+                   "maxima": torch.zeros((B, C, 3), dtype=torch.float64, **kw),
+                   "status": torch.empty(B, dtype=torch.int32, **kw)}
+            flags = nat.MTG_FLAG_DEVICE_PTRS | (nat.MTG_FLAG_ASYNC if asynchronous else 0)
+            self.set_stream(torch.cuda.current_stream(vertex_values.device).cuda_stream)
+        else:
+            vertex_values = np.ascontiguousarray(vertex_values, dtype=np.float64)
+            times = np.ascontiguousarray(times, dtype=np.float64)
+            mask = np.ascontiguousarray(mask, dtype=np.uint8) if mask is not None else None
+            out = {"cost": np.empty(B), "grad": np.zeros((B, D, V * h)) if grad else None,
+                   "maxima": np.zeros((B, C), dtype=EXTREMUM_DTYPE), "status": np.empty(B, np.int32)}
+            flags = 0
+            self.reset_stream()
+        nat.check(self._lib.mtg_soft_constraint_cost_batch(self.handle, N, D, K, B, _addr(vertex_values),
+                                                           _addr(mask) if grad else None, _addr(times),
+                                                           ctypes.byref(p), _addr(out["cost"]), _addr(out["grad"]),
+                                                           _addr(out["maxima"]), _addr(out["status"]), flags),
+                  self.handle)
+        return out
+
     def time_jacobian_batch(self, N, r, vertex_values, times, scales, increment_time=0.0, jacobian=True):
         """Cost sweep + segment-time Jacobian on the matrix cores (include/mtg.h mtg_time_jacobian_batch):
         cost [B][C] = sum_dims d^T R(T_c) d and jac [B][C][K] = dJ/dT_i at T_c (exact for
@@ -505,6 +545,10 @@ def collision_cost_batch(N, vertex_values, times, grid, params, device=0, **kw):
     return default_context(device).collision_cost_batch(N, vertex_values, times, grid, params, **kw)
 
 
+def soft_constraint_cost_batch(N, vertex_values, times, params, device=0, **kw):
+    return default_context(device).soft_constraint_cost_batch(N, vertex_values, times, params, **kw)
+
+
 def shard_range(batch, n_shards, shard):
     """[begin, end) of contiguous shard `shard` of `n_shards` (mtg_shard_range)."""
     b, e = ctypes.c_int64(0), ctypes.c_int64(0)
@@ -610,6 +654,48 @@ def host_collision_cost_batch(N, vertex_values, times, grid, params, mask=None, 
                                                 _addr(out["cost"]), _addr(out.get("grad")), _addr(out["collision"]),
                                                 _addr(out["n_evaluated"]), _addr(out["status"]), threads))
     del keep
+    return out
+
+
+class SoftConstraintParams:
+    """struct mtg_soft_constraint_params (include/mtg.h): the magnitude limits of
+    addMaximumMagnitudeConstraint as (derivative, limit) pairs, with the reference's
+    soft_constraint_weight, maximum cost and finite-difference increment (its map_resolution)."""
+
+    def __init__(self, constraints, weight=100.0, maximum_cost=1e12, increment=0.05):
+        self.constraints = [(int(k), float(v)) for k, v in constraints]
+        self.weight = float(weight)
+        self.maximum_cost = float(maximum_cost)
+        self.increment = float(increment)
+
+    def native(self):
+        n = len(self.constraints)
+        c = self.constraints[:8] + [(0, 0.0)] * (8 - min(n, 8))
+        return nat.SoftConstraintParams(n, (ctypes.c_int32 * 8)(*[k for k, _ in c]),
+                                        (ctypes.c_double * 8)(*[v for _, v in c]), self.weight, self.maximum_cost,
+                                        self.increment)
+
+
+def host_soft_constraint_cost_batch(N, vertex_values, times, params, mask=None, grad=False, threads=1):
+    """The library's host path of Context.soft_constraint_cost_batch (mtg_host_soft_constraint_cost_batch):
+    the reference's loop written literally (every perturbation re-forms and searches the whole
+    trajectory), no GPU.  Same arguments (numpy arrays) and outputs."""
+    lib = nat.load()
+    vertex_values = np.ascontiguousarray(vertex_values, dtype=np.float64)
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    B, V, h, D = vertex_values.shape
+    K = V - 1
+    assert h == N // 2 and times.shape == (B, K)
+    assert not grad or mask is not None, "grad needs mask"
+    mask = np.ascontiguousarray(mask, dtype=np.uint8) if mask is not None else None
+    p = params.native()
+    C = max(int(p.n_constraints), 1)
+    out = {"cost": np.empty(B), "grad": np.zeros((B, D, V * h)) if grad else None,
+           "maxima": np.zeros((B, C), dtype=EXTREMUM_DTYPE), "status": np.empty(B, np.int32)}
+    nat.check(lib.mtg_host_soft_constraint_cost_batch(N, D, K, B, _addr(vertex_values), _addr(mask) if grad else None,
+                                                      _addr(times), ctypes.byref(p), _addr(out["cost"]),
+                                                      _addr(out["grad"]), _addr(out["maxima"]), _addr(out["status"]),
+                                                      threads))
     return out
 
 
