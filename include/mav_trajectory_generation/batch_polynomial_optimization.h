@@ -155,6 +155,42 @@ class BatchPolynomialOptimization {
                                    is_collision, n_evaluated, status, flags),
           ctx_, "mtg_collision_cost_batch");
   }
+  // segment-time gradient of the collision cost, grad_t [B][K] (mtg_collision_time_gradient_batch: the
+  // dJc_dt part of getCostAndGradientTime, nl_impl:2155-2243); D must be 3
+  void collisionTimeGradient(int64_t batch, const double* vertex_values, const double* times, const mtg_sdf_grid& grid,
+                             const mtg_collision_params& params, double* grad_t, double increment_time = 0.1,
+                             double* side_cost = nullptr, int32_t* side_evaluated = nullptr,
+                             int32_t* segments_walked = nullptr, int32_t* status = nullptr, unsigned flags = 0) {
+    check(mtg_collision_time_gradient_batch(ctx_, N, D_, K_, batch, vertex_values, times, &grid, &params,
+                                            increment_time, grad_t, side_cost, side_evaluated, segments_walked, status,
+                                            flags),
+          ctx_, "mtg_collision_time_gradient_batch");
+  }
+  // The complete getCostAndGradientTime (nl_impl:2155-2243) of host arrays: J_t [B] = sum_i T_i and
+  // grad_t [B][K] = (w_d dJd_dt + w_c dJc_dt) + w_t, composed of timeJacobian (one candidate, scales of
+  // 1, the same increment_time) and collisionTimeGradient; the reference's default weights are 0.1, 10,
+  // 1.  Its w_sc dJsc_dt is 0 by its own code (updateSegmentTimes does not rebuild the segments the
+  // soft-constraint term reads) and is left out.  djd_dt / djc_dt [B][K] (nullable) receive the parts.
+  void timeGradient(int64_t batch, const double* vertex_values, const double* times, const mtg_sdf_grid& grid,
+                    const mtg_collision_params& params, double w_d, double w_c, double w_t, double* J_t, double* grad_t,
+                    double increment_time = 0.1, double* djd_dt = nullptr, double* djc_dt = nullptr,
+                    int32_t* status = nullptr) {
+    const size_t n = (size_t)batch * K_;
+    std::vector<double> ones((size_t)K_, 1.0), cost((size_t)batch), jd(n), jc(n);
+    timeJacobian(batch, vertex_values, times, 1, ones.data(), cost.data(), jd.data(), increment_time);
+    collisionTimeGradient(batch, vertex_values, times, grid, params, jc.data(), increment_time, nullptr, nullptr, nullptr,
+                          status);
+    for (int64_t b = 0; b < batch; ++b) {
+      double sum = 0.0;
+      for (int i = 0; i < K_; ++i) sum += times[(size_t)b * K_ + i];
+      if (J_t) J_t[b] = sum;
+    }
+    for (size_t i = 0; i < n; ++i) {
+      grad_t[i] = (w_d * jd[i] + w_c * jc[i]) + w_t;
+      if (djd_dt) djd_dt[i] = jd[i];
+      if (djc_dt) djc_dt[i] = jc[i];
+    }
+  }
   // soft-constraint cost of the magnitude limits (and gradient, packed as costAtTimes' grad)
   // (mtg_soft_constraint_cost_batch: getCostAndGradientSoftConstraints, nl_impl:2025-2091); D <= 4
   void softConstraintCost(int64_t batch, const double* vertex_values, const uint8_t* mask, const double* times,
@@ -220,6 +256,27 @@ inline void collisionCost(int K, int64_t batch, const double* vertex_values, con
     check(mtg_host_collision_cost_batch(N, 3, K, batch, vertex_values, mask, times, &grid, &params, cost, grad,
                                         is_collision, n_evaluated, status, 1),
           nullptr, "mtg_host_collision_cost_batch");
+  }
+}
+
+// The collision part dJc_dt of getCostAndGradientTime (mtg_collision_time_gradient_batch) without a
+// BatchPolynomialOptimization object: on the library's host path
+// (mtg_host_collision_time_gradient_batch, which has no segments_walked diagnostic) unless the
+// execution policy is kDevice, as collisionCost.  Host pointers.
+template <int N>
+inline void collisionTimeGradient(int K, int64_t batch, const double* vertex_values, const double* times,
+                                  const mtg_sdf_grid& grid, const mtg_collision_params& params, double* grad_t,
+                                  double increment_time = 0.1, double* side_cost = nullptr,
+                                  int32_t* side_evaluated = nullptr, int32_t* status = nullptr) {
+  if (singleOnDevice()) {
+    mtg_ctx* ctx = defaultContext();
+    check(mtg_collision_time_gradient_batch(ctx, N, 3, K, batch, vertex_values, times, &grid, &params, increment_time,
+                                            grad_t, side_cost, side_evaluated, nullptr, status, 0),
+          ctx, "mtg_collision_time_gradient_batch");
+  } else {
+    check(mtg_host_collision_time_gradient_batch(N, 3, K, batch, vertex_values, times, &grid, &params, increment_time,
+                                                 grad_t, side_cost, side_evaluated, status, 1),
+          nullptr, "mtg_host_collision_time_gradient_batch");
   }
 }
 

@@ -46,7 +46,8 @@
 extern "C" {
 #endif
 
-#define MTG_ABI_VERSION 2   /* 2: + mtg_soft_constraint_cost_batch, mtg_host_soft_constraint_cost_batch */
+#define MTG_ABI_VERSION 3   /* 2: + mtg_soft_constraint_cost_batch, mtg_host_soft_constraint_cost_batch
+                               3: + mtg_collision_time_gradient_batch, mtg_host_collision_time_gradient_batch */
 
 /* Call-level return codes. */
 #define MTG_OK 0
@@ -372,6 +373,72 @@ int mtg_host_collision_cost_batch(int N, int D, int K, int64_t batch, const doub
                                   const uint8_t* fixed_mask, const double* times, const mtg_sdf_grid* grid,
                                   const mtg_collision_params* params, double* cost_out, double* grad_out,
                                   uint8_t* collision_out, int32_t* n_evaluated_out, int32_t* status, int threads);
+
+/* Segment-time gradient of the collision cost: the dJc_dt part of getCostAndGradientTime
+ * (nl_impl:2155-2243), the central difference of J_c in each segment time, restated as the reference
+ * is written.  D must be 3, N one of 6, 8, 10, 12, K >= 1 up to the LDS limit below.
+ *
+ * The stale L_.  getCostAndGradientTime perturbs a segment time with updateSegmentTimes, which
+ * rebuilds cost_matrices_ and inverse_mapping_matrices_ but does NOT recompute L_: that member is
+ * assigned only at the top of the objective (:1197-1200) and in the optimize* set-ups.
+ * getCostAndGradientCollision forms its coefficients as L_ * d (:1558) and reads its loop bounds from
+ * getSegmentTimes (:1563).  So the perturbed evaluations walk the UNPERTURBED polynomials to a
+ * perturbed end time -- which is why this gradient cannot be composed from mtg_collision_cost_batch
+ * (it re-forms the coefficients from the times it is given).  Per trajectory:
+ *   c_i = A(T_i)^-1 [x_i; x_{i+1}] from `times`, exactly the coefficients of mtg_collision_cost_batch;
+ *   for each segment n and side s (0 = smaller, evaluated first; 1 = bigger) the times T' are
+ *     T'[i] = T[i] for i != n;  T'[n] = 0.1 on BOTH sides if T[n] <= 0.1 (the reference's literal 0.1,
+ *     whatever increment_time is), else T[n] - increment_time (s = 0), T[n] + increment_time (s = 1);
+ *   J_c(n, s) = the loop documented at mtg_collision_cost_batch with those coefficients, the clock
+ *     bound t < T'[i] and the end-of-segment correction time_sum += -dt + (T'[i] - t); the bigger
+ *     side evaluates segment n's polynomial past T[n];
+ *   grad_t[n] = (J_c(n, 1) - J_c(n, 0)) / (2 increment_time).
+ * T[n] <= 0.1 makes the two walks identical and grad_t[n] exactly +0.0.  T[n] > 0.1 with
+ * T[n] - increment_time <= 0: the reference CHECK-fails in updateSegmentTimes; grad_t[n] and both side
+ * costs are NaN and both side counts 0, for that n only (the rule of mtg_time_jacobian_batch).
+ * MTG_TRAJ_BAD_TIME: some T[i] is not positive and finite, or a perturbed time of some segment has
+ * more than 2^24 clock samples ((T[i] + increment_time) / dt, and 0.1 / dt where T[i] <= 0.1); then
+ * every output of the trajectory is NaN and its counts are 0.
+ * MTG_ERR_INVALID_ARGUMENT: increment_time not > 0 and finite (a deviation: the reference would
+ * divide by zero), and the argument errors of mtg_collision_cost_batch.
+ *
+ * vertex_values [B][V][h][3] (ALL derivatives), times [B][K]; grad_t_out [B][K]; side_cost_out
+ * [B][K][2] (nullable): J_c(n, s); side_evaluated_out [B][K][2] (nullable): the samples of that walk
+ * that reached the potential; status [B] (nullable).  Flags and grid staging as
+ * mtg_collision_cost_batch (MTG_FLAG_DEVICE_PTRS, MTG_FLAG_ASYNC).  The nullable outputs do not change
+ * grad_t_out's bits, and results do not depend on the trajectory's place in the batch or on the batch.
+ *
+ * segments_walked_out [B] (nullable, device call only) is a diagnostic of how the kernel avoids 2K
+ * complete walks.  It first walks the unperturbed trajectory once (not counted) and records, at the
+ * entry of every segment m, the loop state (time_sum, dist_sum) and the cost and sample count of the
+ * segments before and from m.  The walk of (n, s) starts from the recorded entry of segment n (the
+ * segments before n are untouched), walks segment n to T'[n] and continues with n+1, n+2, ...  At the
+ * entry of each segment m >= n+2 -- where prev_pos is the last sample of the unperturbed segment m-1
+ * in both walks -- it compares its (time_sum, dist_sum) BIT FOR BIT with the recorded pair: if both
+ * are equal the rest of the walk is the unperturbed one, the recorded sums from m on are added and the
+ * walk stops, having walked m - n segments; if they are never equal it walks to the end (K - n
+ * segments).  segments_walked_out[b] is the sum of those counts over the 2K perturbations (0 for a
+ * perturbation under the NaN rule and for a BAD_TIME trajectory): a function of the inputs alone.
+ * When every perturbation rejoins at n+2 it is 4K - 2.
+ * MTG_ERR_TOO_LARGE: the device call keeps one trajectory (vertex values, coefficients, records) in
+ * 64 KiB of LDS: K <= 204 (N = 6), 166 (8), 140 (10), 121 (12).  The host path has no such limit.
+ * Not covered: the variant that re-forms the coefficients at the perturbed times (what a recomputed
+ * L_ would give); no semantics is invented for it here. */
+int mtg_collision_time_gradient_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* vertex_values,
+                                      const double* times, const mtg_sdf_grid* grid, const mtg_collision_params* params,
+                                      double increment_time, double* grad_t_out, double* side_cost_out,
+                                      int32_t* side_evaluated_out, int32_t* segments_walked_out, int32_t* status,
+                                      unsigned flags);
+
+/* Host (CPU) path of mtg_collision_time_gradient_batch, no context and no GPU needed: the reference
+ * written literally, 2K complete walks per trajectory in the reference's order, in scalar C++ on the
+ * calling thread(s).  The C++ drop-in uses it for single trajectories.  All host pointers;
+ * threads <= 0: mtg_host_default_threads(). */
+int mtg_host_collision_time_gradient_batch(int N, int D, int K, int64_t batch, const double* vertex_values,
+                                           const double* times, const mtg_sdf_grid* grid,
+                                           const mtg_collision_params* params, double increment_time,
+                                           double* grad_t_out, double* side_cost_out, int32_t* side_evaluated_out,
+                                           int32_t* status, int threads);
 
 /* ---- Soft-constraint term of the nonlinear objective (use_soft_constraints, the reference's default,
  * polynomial_optimization_nonlinear.h:57): the magnitude limits added with

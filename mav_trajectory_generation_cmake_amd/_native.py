@@ -113,6 +113,14 @@ _SIGNATURES = {
                                                      _c_dp, _c_dp, ctypes.POINTER(SdfGrid),
                                                      ctypes.POINTER(CollisionParams), _c_dp, _c_dp, _c_dp, _c_dp,
                                                      _c_dp, ctypes.c_int]),
+    "mtg_collision_time_gradient_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                         ctypes.c_int64, _c_dp, _c_dp, ctypes.POINTER(SdfGrid),
+                                                         ctypes.POINTER(CollisionParams), ctypes.c_double, _c_dp, _c_dp,
+                                                         _c_dp, _c_dp, _c_dp, ctypes.c_uint]),
+    "mtg_host_collision_time_gradient_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                              _c_dp, _c_dp, ctypes.POINTER(SdfGrid),
+                                                              ctypes.POINTER(CollisionParams), ctypes.c_double, _c_dp,
+                                                              _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mtg_soft_constraint_cost_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                       ctypes.c_int64, _c_dp, _c_dp, _c_dp,
                                                       ctypes.POINTER(SoftConstraintParams), _c_dp, _c_dp, _c_dp, _c_dp,

@@ -1017,6 +1017,84 @@ int mtg_collision_cost_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, c
   return MTG_OK;
 }
 
+int mtg_collision_time_gradient_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* vertex_values,
+                                      const double* times, const mtg_sdf_grid* grid, const mtg_collision_params* params,
+                                      double increment_time, double* grad_t_out, double* side_cost_out,
+                                      int32_t* side_evaluated_out, int32_t* segments_walked_out, int32_t* status,
+                                      unsigned flags) {
+  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
+  if (N < 6 || N > 12 || (N % 2)) return set_error(ctx, MTG_ERR_UNSUPPORTED_N, "N must be 6, 8, 10 or 12");
+  if (D != 3) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "the collision term needs D == 3");
+  if (K < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need K >= 1, batch >= 0");
+  if (!grid || !params) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "grid and params are required");
+  if (!(params->coll_check_time_increment > 0.0) || !(params->map_resolution >= 0.0) || !(grid->resolution > 0.0) ||
+      grid->nx < 1 || grid->ny < 1 || grid->nz < 1)
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT,
+                     "need coll_check_time_increment > 0, map_resolution >= 0, grid resolution > 0, grid dimensions >= 1");
+  if (!(increment_time > 0.0 && increment_time <= DBL_MAX))
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "increment_time must be > 0 and finite");
+  if (batch == 0) return MTG_OK;
+  if (!vertex_values || !times || !grad_t_out || !grid->distance)
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "vertex_values, times, grad_t_out and grid->distance are required");
+  if (mtg::collision_time_lds_bytes(N, K) > 64 * 1024 || batch > 0x7fffffff)
+    return set_error(ctx, MTG_ERR_TOO_LARGE, "one trajectory's coefficients and walk records exceed LDS (reduce K)");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int V = K + 1, h = N / 2;
+  const size_t b_vals = sizeof(double) * (size_t)batch * V * h * D, b_times = sizeof(double) * (size_t)batch * K,
+               b_grid = sizeof(float) * (size_t)grid->nx * grid->ny * grid->nz, b_grad = sizeof(double) * (size_t)batch * K,
+               b_sc = side_cost_out ? sizeof(double) * (size_t)batch * K * 2 : 0,
+               b_se = side_evaluated_out ? sizeof(int32_t) * (size_t)batch * K * 2 : 0,
+               b_wk = segments_walked_out ? sizeof(int32_t) * (size_t)batch : 0,
+               b_stat = status ? sizeof(int32_t) * (size_t)batch : 0;
+  const double *d_vals = vertex_values, *d_times = times;
+  const float* d_grid = grid->distance;
+  double *d_grad = grad_t_out, *d_sc = side_cost_out;
+  int32_t *d_se = side_evaluated_out, *d_wk = segments_walked_out, *d_stat = status;
+  const bool dev = flags & MTG_FLAG_DEVICE_PTRS;
+  char* base = nullptr;
+  size_t o_grad = 0, o_sc = 0, o_se = 0, o_wk = 0, o_stat = 0;
+  if (!dev) {
+    size_t off = 0;
+    const size_t o_vals = off; off = align_up(off + b_vals);
+    const size_t o_times = off; off = align_up(off + b_times);
+    const size_t o_grid = off; off = align_up(off + b_grid);
+    o_grad = off; off = align_up(off + b_grad);
+    o_sc = off; off = align_up(off + b_sc);
+    o_se = off; off = align_up(off + b_se);
+    o_wk = off; off = align_up(off + b_wk);
+    o_stat = off; off = align_up(off + b_stat);
+    MTG_HIP_TRY(ctx, ensure(&ctx->staging, &ctx->staging_bytes, std::max<size_t>(off, 256)));
+    base = static_cast<char*>(ctx->staging);
+    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_vals, vertex_values, b_vals, hipMemcpyHostToDevice, ctx->stream));
+    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_times, times, b_times, hipMemcpyHostToDevice, ctx->stream));
+    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_grid, grid->distance, b_grid, hipMemcpyHostToDevice, ctx->stream));
+    d_vals = reinterpret_cast<const double*>(base + o_vals);
+    d_times = reinterpret_cast<const double*>(base + o_times);
+    d_grid = reinterpret_cast<const float*>(base + o_grid);
+    d_grad = reinterpret_cast<double*>(base + o_grad);
+    d_sc = b_sc ? reinterpret_cast<double*>(base + o_sc) : nullptr;
+    d_se = b_se ? reinterpret_cast<int32_t*>(base + o_se) : nullptr;
+    d_wk = b_wk ? reinterpret_cast<int32_t*>(base + o_wk) : nullptr;
+    d_stat = b_stat ? reinterpret_cast<int32_t*>(base + o_stat) : nullptr;
+  }
+  MTG_HIP_TRY(ctx, time_begin(ctx));
+  MTG_HIP_TRY(ctx, mtg::launch_collision_time_gradient(N, d_vals, d_times, *grid, d_grid, *params, increment_time, d_grad,
+                                                       d_sc, d_se, d_wk, d_stat, batch, K, ctx->stream));
+  MTG_HIP_TRY(ctx, time_end(ctx));
+  if (!dev) {
+    MTG_HIP_TRY(ctx, hipMemcpyAsync(grad_t_out, base + o_grad, b_grad, hipMemcpyDeviceToHost, ctx->stream));
+    if (b_sc) MTG_HIP_TRY(ctx, hipMemcpyAsync(side_cost_out, base + o_sc, b_sc, hipMemcpyDeviceToHost, ctx->stream));
+    if (b_se) MTG_HIP_TRY(ctx, hipMemcpyAsync(side_evaluated_out, base + o_se, b_se, hipMemcpyDeviceToHost, ctx->stream));
+    if (b_wk) MTG_HIP_TRY(ctx, hipMemcpyAsync(segments_walked_out, base + o_wk, b_wk, hipMemcpyDeviceToHost, ctx->stream));
+    if (b_stat) MTG_HIP_TRY(ctx, hipMemcpyAsync(status, base + o_stat, b_stat, hipMemcpyDeviceToHost, ctx->stream));
+    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  } else if (!(flags & MTG_FLAG_ASYNC)) {
+    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return MTG_OK;
+}
+
 int mtg_soft_constraint_cost_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* vertex_values,
                                    const uint8_t* fixed_mask, const double* times,
                                    const mtg_soft_constraint_params* params, double* cost_out, double* grad_out,

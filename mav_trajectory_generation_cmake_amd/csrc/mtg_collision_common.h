@@ -21,6 +21,24 @@ namespace mtg {
 // t += dt must advance (dt above half an ulp of T), and a single wave must finish.
 constexpr double kCollisionMaxSegmentSamples = 16777216.0;  // 2^24
 
+// ---- the segment-time perturbation of getCostAndGradientTime (nl_impl:2180-2223), shared by
+// mtg_collision_time.hip and mtg_host_collision_time.cpp
+constexpr double kCollisionTimeClamp = 0.1;  // the reference's literal: T_n <= 0.1 gives 0.1 on both sides
+
+// the perturbed time of segment n: side 0 = smaller (evaluated first), 1 = bigger
+MTG_HD double collision_time_perturbed(double T, double inc, int side) {
+  if (T <= kCollisionTimeClamp) return kCollisionTimeClamp;
+  return side ? T + inc : T - inc;
+}
+
+// MTG_TRAJ_BAD_TIME of the time gradient: T not positive and finite, or a perturbed time of this
+// segment (T + inc, or the clamp value) with more than kCollisionMaxSegmentSamples clock samples
+MTG_HD bool collision_time_bad(double T, double inc, double dt) {
+  if (!(T > 0.0 && T <= 1.7976931348623157e308)) return true;
+  if (!((T + inc) / dt <= kCollisionMaxSegmentSamples)) return true;
+  return T <= kCollisionTimeClamp && !(kCollisionTimeClamp / dt <= kCollisionMaxSegmentSamples);
+}
+
 struct CollisionMap {  // mtg_sdf_grid by value
   const float* distance;
   int nx, ny, nz;

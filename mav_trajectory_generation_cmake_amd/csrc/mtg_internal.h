@@ -94,6 +94,14 @@ hipError_t launch_collision_cost(int N, const double* values, const uint8_t* mas
                                  double* cost, double* grad, uint8_t* collision, int32_t* n_evaluated, int32_t* status,
                                  int64_t B, int K, hipStream_t stream);
 
+// segment-time gradient of the collision cost (mtg_collision_time.hip); `distance` is the device copy
+// of grid.distance
+size_t collision_time_lds_bytes(int N, int K);
+hipError_t launch_collision_time_gradient(int N, const double* values, const double* times, const mtg_sdf_grid& grid,
+                                          const float* distance, const mtg_collision_params& p, double increment_time,
+                                          double* grad_t, double* side_cost, int32_t* side_evaluated, int32_t* walked,
+                                          int32_t* status, int64_t B, int K, hipStream_t stream);
+
 // soft-constraint cost / gradient of the magnitude limits (mtg_soft_constraint.hip): threads per block
 // for a shape (0: the trajectory's working set exceeds LDS) and the block's LDS bytes
 int soft_constraint_threads(int N, int D, int K, int C);

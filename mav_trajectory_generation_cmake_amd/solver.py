@@ -299,6 +299,62 @@ class Context:
         del keep
         return out
 
+    def collision_time_gradient_batch(self, N, vertex_values, times, grid, params, increment_time=0.1,
+                                      asynchronous=False, diagnostics=True):
+        """The collision part dJc_dt of getCostAndGradientTime for a batch (include/mtg.h
+        mtg_collision_time_gradient_batch): the central difference of the collision cost in each segment
+        time, walking the unperturbed polynomials to the perturbed end.  Arguments as
+        collision_cost_batch (numpy arrays, or torch CUDA tensors with grid.distance one too).  Returns
+        dict(grad_t [B][K], side_cost [B][K][2], side_evaluated [B][K][2] int32, segments_walked [B] int32,
+        status [B] int32); diagnostics=False passes NULL for everything but grad_t and status (the others
+        are then None; grad_t's bits do not change)."""
+        dev = _is_torch(vertex_values) and vertex_values.is_cuda
+        B, V, h, D = vertex_values.shape
+        K = V - 1
+        assert h == N // 2 and tuple(times.shape) == (B, K)
+        shapes = (("grad_t", (B, K), "f8"), ("side_cost", (B, K, 2), "f8"), ("side_evaluated", (B, K, 2), "i4"),
+                  ("segments_walked", (B,), "i4"), ("status", (B,), "i4"))
+        if dev:
+            import torch
+            assert _is_torch(grid.distance) and grid.distance.is_cuda, "device call: grid.distance must be a CUDA tensor"
+            out = {k: torch.empty(s, dtype=torch.float64 if t == "f8" else torch.int32, device=vertex_values.device)
+                   for k, s, t in shapes}
+            flags = nat.MTG_FLAG_DEVICE_PTRS | (nat.MTG_FLAG_ASYNC if asynchronous else 0)
+            self.set_stream(torch.cuda.current_stream(vertex_values.device).cuda_stream)
+        else:
+            vertex_values = np.ascontiguousarray(vertex_values, dtype=np.float64)
+            times = np.ascontiguousarray(times, dtype=np.float64)
+            out = {k: np.empty(s, dtype=np.float64 if t == "f8" else np.int32) for k, s, t in shapes}
+            flags = 0
+            self.reset_stream()
+        if not diagnostics:
+            out["side_cost"] = out["side_evaluated"] = out["segments_walked"] = None
+        g, keep = grid.native()
+        nat.check(self._lib.mtg_collision_time_gradient_batch(
+            self.handle, N, D, K, B, _addr(vertex_values), _addr(times), ctypes.byref(g), ctypes.byref(params.native()),
+            float(increment_time), _addr(out["grad_t"]), _addr(out["side_cost"]), _addr(out["side_evaluated"]),
+            _addr(out["segments_walked"]), _addr(out["status"]), flags), self.handle)
+        del keep
+        return out
+
+    def time_gradient_batch(self, N, r, vertex_values, times, grid, params, weights=(0.1, 10.0, 1.0), increment_time=0.1):
+        """The complete getCostAndGradientTime (nl_impl:2155-2243) for a batch, composed of
+        time_jacobian_batch (dJd_dt: one candidate, scales of 1, the same increment_time) and
+        collision_time_gradient_batch (dJc_dt).  weights = (w_d, w_c, w_t), the reference's defaults 0.1,
+        10, 1.  The reference's w_sc dJsc_dt is 0 by its own code (updateSegmentTimes does not rebuild
+        the segments its soft-constraint term reads, so it differences two equal numbers) and is left
+        out.  numpy arrays.  Returns dict(J_t [B] = sum_i T_i, grad_t [B][K] = (w_d dJd_dt + w_c dJc_dt) +
+        w_t, dJd_dt, dJc_dt, status [B])."""
+        w_d, w_c, w_t = (float(w) for w in weights)
+        times = np.ascontiguousarray(times, dtype=np.float64)
+        K = times.shape[1]
+        _, jd = self.time_jacobian_batch(N, r, vertex_values, times, np.ones((1, K)), increment_time=increment_time)
+        c = self.collision_time_gradient_batch(N, vertex_values, times, grid, params, increment_time=increment_time,
+                                               diagnostics=False)
+        jd = jd[:, 0, :]
+        return {"J_t": times.sum(1), "grad_t": (w_d * jd + w_c * c["grad_t"]) + w_t, "dJd_dt": jd, "dJc_dt": c["grad_t"],
+                "status": c["status"]}
+
     def soft_constraint_cost_batch(self, N, vertex_values, times, params, mask=None, grad=False, asynchronous=False):
         """getCostAndGradientSoftConstraints for a batch (include/mtg.h mtg_soft_constraint_cost_batch):
         vertex_values [B][V][h][D] (all derivatives), times [B][K], params a SoftConstraintParams.  numpy
@@ -549,6 +605,14 @@ def soft_constraint_cost_batch(N, vertex_values, times, params, device=0, **kw):
     return default_context(device).soft_constraint_cost_batch(N, vertex_values, times, params, **kw)
 
 
+def collision_time_gradient_batch(N, vertex_values, times, grid, params, device=0, **kw):
+    return default_context(device).collision_time_gradient_batch(N, vertex_values, times, grid, params, **kw)
+
+
+def time_gradient_batch(N, r, vertex_values, times, grid, params, device=0, **kw):
+    return default_context(device).time_gradient_batch(N, r, vertex_values, times, grid, params, **kw)
+
+
 def shard_range(batch, n_shards, shard):
     """[begin, end) of contiguous shard `shard` of `n_shards` (mtg_shard_range)."""
     b, e = ctypes.c_int64(0), ctypes.c_int64(0)
@@ -653,6 +717,27 @@ def host_collision_cost_batch(N, vertex_values, times, grid, params, mask=None, 
                                                 _addr(times), ctypes.byref(g), ctypes.byref(params.native()),
                                                 _addr(out["cost"]), _addr(out.get("grad")), _addr(out["collision"]),
                                                 _addr(out["n_evaluated"]), _addr(out["status"]), threads))
+    del keep
+    return out
+
+
+def host_collision_time_gradient_batch(N, vertex_values, times, grid, params, increment_time=0.1, threads=1):
+    """The library's host path of Context.collision_time_gradient_batch
+    (mtg_host_collision_time_gradient_batch): the reference written literally, 2K complete walks per
+    trajectory, no GPU.  Same arguments (numpy arrays) and outputs, without segments_walked."""
+    lib = nat.load()
+    vertex_values = np.ascontiguousarray(vertex_values, dtype=np.float64)
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    B, V, h, D = vertex_values.shape
+    K = V - 1
+    assert h == N // 2 and times.shape == (B, K)
+    out = {"grad_t": np.empty((B, K)), "side_cost": np.empty((B, K, 2)), "side_evaluated": np.empty((B, K, 2), np.int32),
+           "status": np.empty(B, np.int32)}
+    g, keep = grid.native()
+    nat.check(lib.mtg_host_collision_time_gradient_batch(N, D, K, B, _addr(vertex_values), _addr(times), ctypes.byref(g),
+                                                         ctypes.byref(params.native()), float(increment_time),
+                                                         _addr(out["grad_t"]), _addr(out["side_cost"]),
+                                                         _addr(out["side_evaluated"]), _addr(out["status"]), threads))
     del keep
     return out
 
