@@ -200,6 +200,22 @@ class BatchPolynomialOptimization {
                                          maxima, status, flags),
           ctx_, "mtg_soft_constraint_cost_batch");
   }
+  // The reference's nonlinear objective in the optimiser's variables, one cost and one gradient per
+  // trajectory (mtg_objective_batch: objectiveFunctionFreeConstraints[AndCollision[AndTime]],
+  // nl_impl:909-1449).  x [B][x_stride]: (objective 2: the K times, then) D blocks of n_free[b] free
+  // derivatives; params.derivative_to_optimize is set to this object's.  grid / collision NULL for
+  // objective 0, soft NULL iff !params.use_soft_constraints, times NULL for objective 2.
+  void objective(int64_t batch, const double* values, const uint8_t* mask, const double* times, const double* x,
+                 int64_t x_stride, mtg_objective_params params, const mtg_sdf_grid* grid,
+                 const mtg_collision_params* collision, const mtg_soft_constraint_params* soft, double* cost,
+                 double* grad = nullptr, double* weighted_costs = nullptr, uint8_t* is_collision = nullptr,
+                 mtg_objective_state* state = nullptr, const mtg_objective_parts* parts = nullptr,
+                 int32_t* status = nullptr, unsigned flags = 0) {
+    params.derivative_to_optimize = r_;
+    check(mtg_objective_batch(ctx_, N, D_, K_, batch, values, mask, times, x, x_stride, &params, grid, collision, soft,
+                              cost, grad, weighted_costs, is_collision, state, parts, status, flags),
+          ctx_, "mtg_objective_batch");
+  }
   void coefficientsFromVertices(int64_t batch, const double* vertex_values, const double* times, double* coeffs,
                                 unsigned flags = 0) {
     check(mtg_coefficients_from_vertices_batch(ctx_, N, D_, K_, batch, vertex_values, times, coeffs, flags), ctx_,
@@ -297,6 +313,29 @@ inline void softConstraintCost(int D, int K, int64_t batch, const double* vertex
     check(mtg_host_soft_constraint_cost_batch(N, D, K, batch, vertex_values, mask, times, &params, cost, grad, maxima,
                                               status, 1),
           nullptr, "mtg_host_soft_constraint_cost_batch");
+  }
+}
+
+// The nonlinear objective in the optimiser's variables (mtg_objective_batch) for trajectories of N
+// coefficients, K segments and D dimensions, without a BatchPolynomialOptimization object: on the
+// library's host path (mtg_host_objective_batch) unless the execution policy is kDevice, as
+// collisionCost.  Host pointers.
+template <int N>
+inline void objective(int D, int K, int64_t batch, const double* values, const uint8_t* mask, const double* times,
+                      const double* x, int64_t x_stride, const mtg_objective_params& params, const mtg_sdf_grid* grid,
+                      const mtg_collision_params* collision, const mtg_soft_constraint_params* soft, double* cost,
+                      double* grad = nullptr, double* weighted_costs = nullptr, uint8_t* is_collision = nullptr,
+                      mtg_objective_state* state = nullptr, const mtg_objective_parts* parts = nullptr,
+                      int32_t* status = nullptr) {
+  if (singleOnDevice()) {
+    mtg_ctx* ctx = defaultContext();
+    check(mtg_objective_batch(ctx, N, D, K, batch, values, mask, times, x, x_stride, &params, grid, collision, soft, cost,
+                              grad, weighted_costs, is_collision, state, parts, status, 0),
+          ctx, "mtg_objective_batch");
+  } else {
+    check(mtg_host_objective_batch(N, D, K, batch, values, mask, times, x, x_stride, &params, grid, collision, soft, cost,
+                                   grad, weighted_costs, is_collision, state, parts, status, 1),
+          nullptr, "mtg_host_objective_batch");
   }
 }
 

@@ -46,8 +46,9 @@
 extern "C" {
 #endif
 
-#define MTG_ABI_VERSION 3   /* 2: + mtg_soft_constraint_cost_batch, mtg_host_soft_constraint_cost_batch
-                               3: + mtg_collision_time_gradient_batch, mtg_host_collision_time_gradient_batch */
+#define MTG_ABI_VERSION 4   /* 2: + mtg_soft_constraint_cost_batch, mtg_host_soft_constraint_cost_batch
+                               3: + mtg_collision_time_gradient_batch, mtg_host_collision_time_gradient_batch
+                               4: + mtg_objective_batch, mtg_host_objective_batch, mtg_host_objective_bounds_batch */
 
 /* Call-level return codes. */
 #define MTG_OK 0
@@ -66,6 +67,9 @@ extern "C" {
 #define MTG_TRAJ_NOT_SPD 2             /* non-positive pivot in R_pp (reference: undetected, lin_impl:355-368),
                                           or some 0 < T < DBL_EPSILON, where the reference's A(T) is
                                           singular (baseCoeffsWithTime, polynomial.h:225) */
+#define MTG_TRAJ_ROW_TOO_SHORT 4        /* mtg_objective_batch with MTG_FLAG_DEVICE_PTRS: x_stride is shorter than
+                                          this trajectory's row (a host-pointer call returns
+                                          MTG_ERR_INVALID_ARGUMENT instead); its x is not read */
 #define MTG_TRAJ_WARN_DROPPED 256      /* constraint of order > N/2-1 ignored (LOG(WARNING) lin_impl:84-87) */
 #define MTG_TRAJ_ERROR_MASK 255
 
@@ -498,6 +502,152 @@ int mtg_host_soft_constraint_cost_batch(int N, int D, int K, int64_t batch, cons
                                         const uint8_t* fixed_mask, const double* times,
                                         const mtg_soft_constraint_params* params, double* cost_out,
                                         double* grad_out, mtg_extremum* maxima_out, int32_t* status, int threads);
+
+/* ---- The nonlinear objective in the optimiser's variables: what nlopt calls once per iteration in
+ * PolynomialOptimizationNonLinear<N> (nl_impl:909-1449), one cost and one gradient per trajectory,
+ * composed on the device from the five entry points above. */
+#define MTG_OBJECTIVE_FREE_CONSTRAINTS 0                        /* objectiveFunctionFreeConstraints, nl_impl:909-1000 */
+#define MTG_OBJECTIVE_FREE_CONSTRAINTS_AND_COLLISION 1          /* ...AndCollision, nl_impl:1003-1156 */
+#define MTG_OBJECTIVE_FREE_CONSTRAINTS_AND_COLLISION_AND_TIME 2 /* ...AndCollisionAndTime, nl_impl:1159-1449 */
+/* Not covered, MTG_ERR_INVALID_ARGUMENT: the two solve-based objectives (objectiveFunctionTime,
+ * objectiveFunctionTimeAndConstraints) as values of `objective`, and the reference's numerical-gradient
+ * switches as bits of mtg_objective_params.reserved (any non-zero `reserved` is rejected). */
+#define MTG_OBJECTIVE_TIME 3                                    /* not covered */
+#define MTG_OBJECTIVE_TIME_AND_CONSTRAINTS 4                    /* not covered */
+#define MTG_OBJECTIVE_USE_NUMERIC_GRAD 1                        /* use_numeric_grad: not covered */
+#define MTG_OBJECTIVE_SIMPLE_NUMGRAD_TIME 2                     /* is_simple_numgrad_time: not covered */
+#define MTG_OBJECTIVE_SIMPLE_NUMGRAD_CONSTRAINTS 4              /* is_simple_numgrad_constraints: not covered */
+
+typedef struct mtg_objective_params {
+  int32_t objective;                /* MTG_OBJECTIVE_* */
+  int32_t derivative_to_optimize;
+  double  w_d, w_c, w_t, w_sc;      /* reference defaults 0.1, 10, 1, 1 */
+  double  increment_time;           /* reference default 0.1; used by objective 2 only */
+  int32_t use_soft_constraints;     /* reference default true */
+  int32_t is_collision_safe;        /* objective 2 only */
+  int32_t is_coll_raise_first_iter; /* objective 2 only */
+  int32_t reserved;                 /* must be 0 (see the not-covered switches above) */
+  double  add_coll_raise;
+} mtg_objective_params;
+
+/* optimization_info_ + total_cost_iter0_ + is_iter0_ of one problem; all-zero bytes = a fresh optimisation */
+typedef struct mtg_objective_state {
+  double  total_cost_iter0;
+  double  cost_trajectory, cost_collision, cost_time, cost_soft_constraints;
+  int32_t n_iterations;
+  int32_t iter0_done;
+} mtg_objective_state;
+
+/* The unweighted parts, exactly as the component entry points return them (also for a trajectory
+ * with an error status: the NaN rule below applies to the objective's own outputs only).  Every
+ * pointer is nullable; a gradient part is filled only when grad_out is given and the objective uses it. */
+typedef struct mtg_objective_parts {
+  double *J_d, *J_c, *J_sc, *J_t;       /* [B] */
+  double *dJd_dt, *dJc_dt;              /* [B][K]       (objective 2) */
+  double *grad_d, *grad_c, *grad_sc;    /* [B][D][V*h], the packing of mtg_cost_at_times_batch */
+} mtg_objective_parts;
+
+/* One evaluation of the objective per trajectory.  values / fixed_mask are the problem as
+ * mtg_solve_linear_batch reads it; row b of x [B][x_stride] is the vector nlopt sees:
+ *   objective 2: the K segment times first (objectives 0 and 1 have none and read `times` [B][K];
+ *                objective 2 takes times == NULL),
+ *   then D blocks of n_free[b] free derivatives in the reference's (vertex, derivative) order;
+ *   n_free[b] = the derivatives below h that fixed_mask[b] does not fix (bit 7 and bits >= h are
+ *   ignored); it may differ between trajectories and may be 0.
+ * x_stride must be at least the longest row (else MTG_ERR_INVALID_ARGUMENT; with MTG_FLAG_DEVICE_PTRS
+ * the mask is not read on the host: x_stride < (objective 2: K) + D V h is then checked per trajectory on
+ * the device and reported as MTG_TRAJ_ROW_TOO_SHORT, an error bit like the others).  Entries of x past a row's
+ * length are not read; entries of grad_out [B][x_stride] past it are written as +0.0.
+ *
+ * Semantics.  Every product and every sum below rounds on its own and is evaluated left to right.
+ *   vertex_values = the fixed values from `values`, the free ones from x (setFreeConstraints); T = the
+ *     times (objective 2: from x).
+ *   J_d, grad_d   = mtg_cost_at_times_batch with one candidate and scales of 1.
+ *   J_c, grad_c, is_collision = mtg_collision_cost_batch.
+ *   J_sc, grad_sc = mtg_soft_constraint_cost_batch; both 0 when use_soft_constraints is off.
+ * Objective 0: cost = J_d + J_sc (unweighted, as the reference's TODO leaves it); grad = grad_d (the
+ *   reference does not add grad_sc there).  State: n_iterations++, cost_trajectory = J_d,
+ *   cost_soft_constraints = J_sc, nothing else.
+ * Objective 1: ct = w_d J_d, cc = w_c J_c, cs = w_sc J_sc; cost = (ct + cc) + cs;
+ *   grad = (w_d grad_d + w_c grad_c) + w_sc grad_sc.  State: n_iterations++, the three costs; if
+ *   !iter0_done: total_cost_iter0 = cost, iter0_done = 1.  There is no raise.
+ * Objective 2: J_t = T_0 + T_1 + ... (sequential, computeTotalTrajectoryTime);
+ *   grad_t[n] = ((w_d dJd_dt[n] + w_c dJc_dt[n]) + w_sc * 0.0) + w_t, with dJd_dt from
+ *   mtg_time_jacobian_batch (one candidate, scales of 1, increment_time) and dJc_dt from
+ *   mtg_collision_time_gradient_batch; the soft-constraint time term is the reference's exact zero (see
+ *   mtg_soft_constraint_cost_batch).  The free-derivative gradient is that of objective 1.
+ *   ct, cc, cs as above, ctime = w_t J_t, total = ((ct + cc) + ctime) + cs.
+ *   If is_collision_safe and is_collision, the cost may be raised:
+ *     with is_coll_raise_first_iter: if total < state.total_cost_iter0 then
+ *       cc = (state.total_cost_iter0 - (total - cc)) + add_coll_raise;
+ *     otherwise the same with last = ((state.cost_trajectory + state.cost_collision) + state.cost_time)
+ *       + state.cost_soft_constraints in place of total_cost_iter0.
+ *   cost = ((ct + cc) + ctime) + cs with the possibly raised cc.  State: n_iterations++, the four
+ *   costs; if !iter0_done: total_cost_iter0 = cost, iter0_done = 1 (after the raise, as the reference
+ *   orders it).  The gradient is not touched by the raise.
+ * state == NULL behaves as an all-zero state that is thrown away.
+ * weighted_costs_out [B][4] = trajectory, collision (after the raise), time, soft constraints as the
+ *   state receives them (objective 0: J_d, 0, 0, J_sc; objective 1: time = 0).
+ * grad_out == NULL is the reference's gradient.empty() branch: no gradient work is launched (no grad_*,
+ *   no dJ*_dt) and the bits of cost_out, weighted_costs_out, collision_out and state do not change.
+ *
+ * Shapes and argument errors are those of the entry points used: objectives 1 and 2 need D = 3 and N in
+ * {6, 8, 10, 12} and take the smaller of the components' LDS limits on K (MTG_ERR_TOO_LARGE);
+ * objective 0 takes 1 <= D <= 4.  grid / collision are NULL for objective 0, soft is NULL iff
+ * !use_soft_constraints; the param structs are host structs read during the call.
+ * status [B] (nullable) is the OR of the components' statuses (the bits of mtg_solve_linear_batch) and
+ * of MTG_TRAJ_BAD_TIME where a time is not positive and finite (a time <= 0 in x is such a case).  For a
+ * trajectory with an error bit every floating output of its row is NaN (the padding of grad_out stays
+ * +0.0), collision_out is 0 and its state is left as it was.
+ *
+ * Device call: an unpack kernel, the component kernels and a combine kernel on the context's stream,
+ * no host synchronisation between them; intermediates live in a context-owned workspace
+ * (DESIGN.md).  MTG_FLAG_DEVICE_PTRS (every array, parts' pointers and grid->distance included) and
+ * MTG_FLAG_ASYNC as in the collision entries; a host-pointer call stages inputs and the requested
+ * outputs once each. */
+int mtg_objective_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* values,
+                        const uint8_t* fixed_mask, const double* times, const double* x, int64_t x_stride,
+                        const mtg_objective_params* params, const mtg_sdf_grid* grid,
+                        const mtg_collision_params* collision, const mtg_soft_constraint_params* soft,
+                        double* cost_out, double* grad_out, double* weighted_costs_out, uint8_t* collision_out,
+                        mtg_objective_state* state, const mtg_objective_parts* parts, int32_t* status, unsigned flags);
+
+/* Host (CPU) path of mtg_objective_batch, no context and no GPU needed: composed of
+ * mtg_host_collision_cost_batch, mtg_host_soft_constraint_cost_batch,
+ * mtg_host_collision_time_gradient_batch and a host evaluation of the derivative term:
+ * J_d = sum_dims sum_segments e^T H(T_i) e with H as mtg_host_segment_matrices returns it,
+ * grad_d = 2 (R d)_free, dJd_dt by the reference's central difference of J_d with the rules of
+ * mtg_time_jacobian_batch (0 where T_i <= 0.1, NaN where T_i - increment_time <= 0).  The combination
+ * is the same code as the device's.  All host pointers; threads <= 0: mtg_host_default_threads(). */
+int mtg_host_objective_batch(int N, int D, int K, int64_t batch, const double* values, const uint8_t* fixed_mask,
+                             const double* times, const double* x, int64_t x_stride,
+                             const mtg_objective_params* params, const mtg_sdf_grid* grid,
+                             const mtg_collision_params* collision, const mtg_soft_constraint_params* soft,
+                             double* cost_out, double* grad_out, double* weighted_costs_out, uint8_t* collision_out,
+                             mtg_objective_state* state, const mtg_objective_parts* parts, int32_t* status,
+                             int threads);
+
+/* Bounds and initial step of the optimiser's variables (host only), restated literally, index arithmetic
+ * included: setFreeEndpointDerivativeHardConstraints (nl_impl:2518-2564) and the time bounds and
+ * initial step of nl_impl:646-692.  x [B][x_stride] in the layout of mtg_objective_batch, with the K
+ * times first when with_times is set.  Per trajectory, with nf = n_free[b] and r = derivative_to_optimize:
+ *   times: lower 0.1, upper +inf;  every free derivative: -inf / +inf, then
+ *   for k < D, n < K - 1:
+ *     start = k nf + n r              (solve_with_position_constraint)
+ *     start = k nf + n (r + 1), lower[start] = min_bound[k], upper[start] = max_bound[k]   (otherwise)
+ *     for each constraint c: idx = start + derivative_c - 1 (with position constraint; unsigned, so
+ *       derivative 0 wraps) or start + derivative_c; lower[idx] = -|limit_c|, upper[idx] = |limit_c|
+ *   initial_step = initial_stepsize_rel * |x|.
+ * An index the reference's .at() would throw on (>= D nf) gives MTG_ERR_INVALID_ARGUMENT.
+ * constraints may be NULL (none; only n_constraints, derivative and limit are read); min_bound /
+ * max_bound [D] are read only without the position constraint.  lower, upper, initial_step
+ * [B][x_stride] (each nullable); entries past a row's length are +0.0. */
+int mtg_host_objective_bounds_batch(int N, int D, int K, int64_t batch, const uint8_t* fixed_mask, int with_times,
+                                    const double* x, int64_t x_stride, int derivative_to_optimize,
+                                    int solve_with_position_constraint,
+                                    const mtg_soft_constraint_params* constraints, const double* min_bound,
+                                    const double* max_bound, double initial_stepsize_rel, double* lower,
+                                    double* upper, double* initial_step);
 
 /* Timing of the most recent kernel launch(es) of this context on its stream
  * (hipEvent pair around the solve kernel), in milliseconds. */

@@ -24,6 +24,7 @@ MTG_ERR_TOO_LARGE = -8
 MTG_TRAJ_OK = 0
 MTG_TRAJ_BAD_TIME = 1
 MTG_TRAJ_NOT_SPD = 2
+MTG_TRAJ_ROW_TOO_SHORT = 4
 MTG_TRAJ_WARN_DROPPED = 256
 MTG_TRAJ_ERROR_MASK = 255
 
@@ -43,6 +44,15 @@ MTG_KERNEL_DLX = 7
 KERNEL_NAMES = {MTG_KERNEL_COLUMN: "solve_reg_kernel",
                 MTG_KERNEL_GENERAL: "solve_fused_kernel", MTG_KERNEL_SPLIT: "assemble+block_cholesky",
                 MTG_KERNEL_DL: "solve_dl_kernel", MTG_KERNEL_DLX: "solve_dlx_kernel"}
+
+MTG_OBJECTIVE_FREE_CONSTRAINTS = 0
+MTG_OBJECTIVE_FREE_CONSTRAINTS_AND_COLLISION = 1
+MTG_OBJECTIVE_FREE_CONSTRAINTS_AND_COLLISION_AND_TIME = 2
+MTG_OBJECTIVE_TIME = 3                      # not covered
+MTG_OBJECTIVE_TIME_AND_CONSTRAINTS = 4      # not covered
+MTG_OBJECTIVE_USE_NUMERIC_GRAD = 1          # bits of ObjectiveParams.reserved: not covered
+MTG_OBJECTIVE_SIMPLE_NUMGRAD_TIME = 2
+MTG_OBJECTIVE_SIMPLE_NUMGRAD_CONSTRAINTS = 4
 
 _c_dp = ctypes.c_void_p  # every array argument is passed as a raw address
 
@@ -66,6 +76,21 @@ class SoftConstraintParams(ctypes.Structure):
     """struct mtg_soft_constraint_params (include/mtg.h)."""
     _fields_ = [("n_constraints", ctypes.c_int32), ("derivative", ctypes.c_int32 * 8), ("limit", ctypes.c_double * 8),
                 ("weight", ctypes.c_double), ("maximum_cost", ctypes.c_double), ("increment", ctypes.c_double)]
+
+
+class ObjectiveParams(ctypes.Structure):
+    """struct mtg_objective_params (include/mtg.h)."""
+    _fields_ = [("objective", ctypes.c_int32), ("derivative_to_optimize", ctypes.c_int32), ("w_d", ctypes.c_double),
+                ("w_c", ctypes.c_double), ("w_t", ctypes.c_double), ("w_sc", ctypes.c_double),
+                ("increment_time", ctypes.c_double), ("use_soft_constraints", ctypes.c_int32),
+                ("is_collision_safe", ctypes.c_int32), ("is_coll_raise_first_iter", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("add_coll_raise", ctypes.c_double)]
+
+
+class ObjectiveParts(ctypes.Structure):
+    """struct mtg_objective_parts (include/mtg.h): nine nullable double pointers."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("J_d", "J_c", "J_sc", "J_t", "dJd_dt", "dJc_dt", "grad_d", "grad_c",
+                                               "grad_sc")]
 
 
 _SIGNATURES = {
@@ -128,6 +153,21 @@ _SIGNATURES = {
     "mtg_host_soft_constraint_cost_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                                            _c_dp, _c_dp, _c_dp, ctypes.POINTER(SoftConstraintParams),
                                                            _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mtg_objective_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                           _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int64, ctypes.POINTER(ObjectiveParams),
+                                           ctypes.POINTER(SdfGrid), ctypes.POINTER(CollisionParams),
+                                           ctypes.POINTER(SoftConstraintParams), _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                           ctypes.POINTER(ObjectiveParts), _c_dp, ctypes.c_uint]),
+    "mtg_host_objective_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int64,
+                                                ctypes.POINTER(ObjectiveParams), ctypes.POINTER(SdfGrid),
+                                                ctypes.POINTER(CollisionParams), ctypes.POINTER(SoftConstraintParams),
+                                                _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.POINTER(ObjectiveParts), _c_dp,
+                                                ctypes.c_int]),
+    "mtg_host_objective_bounds_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _c_dp,
+                                                       ctypes.c_int, _c_dp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                                       ctypes.POINTER(SoftConstraintParams), _c_dp, _c_dp,
+                                                       ctypes.c_double, _c_dp, _c_dp, _c_dp]),
     "mtg_time_jacobian_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_int64, _c_dp, _c_dp, ctypes.c_int, _c_dp,
                                                ctypes.c_double, _c_dp, _c_dp, ctypes.c_uint]),

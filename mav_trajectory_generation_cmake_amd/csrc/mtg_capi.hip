@@ -1226,6 +1226,232 @@ int mtg_time_jacobian_batch(mtg_ctx* ctx, int N, int D, int K, int derivative_to
   return MTG_OK;
 }
 
+// The objective in the optimiser's variables.  Launch sequence on the context's stream, no host
+// synchronisation in between: unpack | cost | [collision] | [soft] | [jacobian |
+// collision-time] | combine.  The component LAUNCHERS are called, not the entry points above, so
+// nothing is staged twice; intermediates live in ctx->workspace.
+int mtg_objective_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* values,
+                        const uint8_t* fixed_mask, const double* times, const double* x, int64_t x_stride,
+                        const mtg_objective_params* params, const mtg_sdf_grid* grid,
+                        const mtg_collision_params* collision, const mtg_soft_constraint_params* soft,
+                        double* cost_out, double* grad_out, double* weighted_costs_out, uint8_t* collision_out,
+                        mtg_objective_state* state, const mtg_objective_parts* parts, int32_t* status, unsigned flags) {
+  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
+  if (!params) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "params are required");
+  const int obj = params->objective;
+  if (obj < MTG_OBJECTIVE_FREE_CONSTRAINTS || obj > MTG_OBJECTIVE_FREE_CONSTRAINTS_AND_COLLISION_AND_TIME)
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "objective not covered (the solve-based objectives are not)");
+  if (params->reserved != 0)
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "reserved must be 0 (the numerical-gradient switches are not covered)");
+  const bool with_coll = obj != MTG_OBJECTIVE_FREE_CONSTRAINTS;
+  const bool with_time = obj == MTG_OBJECTIVE_FREE_CONSTRAINTS_AND_COLLISION_AND_TIME;
+  const bool with_soft = params->use_soft_constraints != 0;
+  const bool with_grad = grad_out != nullptr;
+  const int r = params->derivative_to_optimize;
+  int rc = check_shape(ctx, N, D, K, r, batch);
+  if (rc != MTG_OK) return rc;
+  if (with_coll) {
+    if (N < 6) return set_error(ctx, MTG_ERR_UNSUPPORTED_N, "N must be 6, 8, 10 or 12");
+    if (D != 3) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "the collision term needs D == 3");
+    if (!grid || !collision) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "grid and collision params are required");
+    if (!(collision->coll_check_time_increment > 0.0) || !(collision->map_resolution >= 0.0) ||
+        !(grid->resolution > 0.0) || grid->nx < 1 || grid->ny < 1 || grid->nz < 1)
+      return set_error(ctx, MTG_ERR_INVALID_ARGUMENT,
+                       "need coll_check_time_increment > 0, map_resolution >= 0, grid resolution > 0, grid dimensions >= 1");
+    if (with_time && !(params->increment_time > 0.0 && params->increment_time <= DBL_MAX))
+      return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "increment_time must be > 0 and finite");
+  } else if (D > 4) {
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "objective 0 needs 1 <= D <= 4");
+  }
+  if (with_soft != (soft != nullptr))
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "soft params are required iff use_soft_constraints");
+  int C = 0;
+  if (with_soft) {
+    if (N < 6 || D > 4) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "the soft-constraint term needs N >= 6, D <= 4");
+    if (soft->n_constraints < 1 || soft->n_constraints > 8)
+      return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "need 1 <= n_constraints <= 8");
+    C = soft->n_constraints;
+    const int kmax = N - 2 < 4 ? N - 2 : 4;
+    for (int c = 0; c < C; ++c)
+      if (soft->derivative[c] < 0 || soft->derivative[c] > kmax || !(soft->limit[c] > 0.0))
+        return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "need 0 <= derivative <= min(4, N - 2) and limit > 0");
+  }
+  if (x_stride < 0) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "x_stride must be >= 0");
+  if (batch == 0) return MTG_OK;
+  if (!values || !fixed_mask || !cost_out || !x || (!with_time && !times) ||
+      (with_coll && !grid->distance))
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT,
+                     "values, fixed_mask, x, cost_out (objectives 0, 1: times; 1, 2: grid->distance) are required");
+  const int V = K + 1, h = N / 2;
+  const bool dev = flags & MTG_FLAG_DEVICE_PTRS;
+  const int nt = with_time ? K : 0;
+  if (!dev) {  // the longest row must fit (a device-pointer call checks per trajectory in the unpack kernel)
+    int64_t longest = 0;
+    for (int64_t b = 0; b < batch; ++b)
+      longest = std::max<int64_t>(longest, nt + (int64_t)D * mtg::objective_n_free(fixed_mask + b * V, V, h));
+    if (x_stride < longest) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "x_stride is shorter than the longest row");
+  }
+  if (mtg::cost_lds_bytes(N, D, K) > 64 * 1024 || (with_coll && mtg::collision_lds_bytes(N, K) > 64 * 1024) ||
+      (with_soft && mtg::soft_constraint_threads(N, D, K, C) == 0) ||
+      (with_time && with_grad &&
+       (mtg::collision_time_lds_bytes(N, K) > 64 * 1024 || mtg::time_jacobian_lds_bytes(N, D, K, 1) > 160 * 1024)) ||
+      batch > 0x7fffffff || (double)batch * (double)std::max<int64_t>((int64_t)V * h * D, x_stride) > 5e11)
+    return set_error(ctx, MTG_ERR_TOO_LARGE, "a component's per-trajectory working set exceeds LDS (reduce K), or the batch is too large");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+  // ---- workspace: every intermediate of the call
+  const size_t nB = (size_t)batch;
+  const size_t b_vv = sizeof(double) * nB * V * h * D, b_T = sizeof(double) * nB * K, b_s = sizeof(double) * nB,
+               b_g = with_grad ? sizeof(double) * nB * D * V * h : 0, b_jt = with_time && with_grad ? b_T : 0,
+               b_i = sizeof(int32_t) * nB;
+  size_t woff = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = woff;
+    woff = align_up(woff + bytes);
+    return o;
+  };
+  const size_t w_vv = take(b_vv), w_T = take(b_T), w_ones = take(sizeof(double) * K), w_Jd = take(b_s), w_Jc = take(b_s),
+               w_Jsc = take(b_s), w_Jt = take(b_s), w_Jd2 = take(b_s), w_gd = take(b_g), w_gc = take(with_coll ? b_g : 0),
+               w_gsc = take(with_coll && with_soft ? b_g : 0), w_jd = take(b_jt), w_jc = take(b_jt), w_coll = take(nB),
+               w_nf = take(b_i), w_su = take(b_i), w_sc = take(b_i), w_ss = take(b_i), w_st = take(b_i);
+  MTG_HIP_TRY(ctx, ensure(&ctx->workspace, &ctx->workspace_bytes, std::max<size_t>(woff, 256)));
+  char* ws = static_cast<char*>(ctx->workspace);
+  auto wd = [&](size_t o) { return reinterpret_cast<double*>(ws + o); };
+  auto wi = [&](size_t o) { return reinterpret_cast<int32_t*>(ws + o); };
+
+  // ---- staging of a host-pointer call: inputs and the objective's own outputs (the parts are copied
+  // out of the workspace)
+  const size_t b_x = sizeof(double) * nB * (size_t)x_stride, b_mask = nB * V, b_state = state ? sizeof(mtg_objective_state) * nB : 0,
+               b_grid = with_coll ? sizeof(float) * (size_t)grid->nx * grid->ny * grid->nz : 0,
+               b_grad = with_grad ? b_x : 0, b_w = weighted_costs_out ? 4 * b_s : 0, b_co = collision_out ? nB : 0,
+               b_stat = status ? b_i : 0;
+  const double *d_x = x, *d_vals = values, *d_times = times;
+  const uint8_t* d_mask = fixed_mask;
+  const float* d_grid = with_coll ? grid->distance : nullptr;
+  double *d_cost = cost_out, *d_grad = grad_out, *d_w = weighted_costs_out;
+  uint8_t* d_co = collision_out;
+  mtg_objective_state* d_state = state;
+  int32_t* d_stat = status;
+  char* base = nullptr;
+  size_t o_cost = 0, o_grad = 0, o_w = 0, o_co = 0, o_state = 0, o_stat = 0;
+  if (!dev) {
+    size_t off = 0;
+    const size_t o_x = off; off = align_up(off + b_x);
+    const size_t o_vals = off; off = align_up(off + b_vv);
+    const size_t o_mask = off; off = align_up(off + b_mask);
+    const size_t o_times = off; off = align_up(off + (with_time ? 0 : b_T));
+    const size_t o_grid = off; off = align_up(off + b_grid);
+    o_state = off; off = align_up(off + b_state);
+    o_cost = off; off = align_up(off + b_s);
+    o_grad = off; off = align_up(off + b_grad);
+    o_w = off; off = align_up(off + b_w);
+    o_co = off; off = align_up(off + b_co);
+    o_stat = off; off = align_up(off + b_stat);
+    MTG_HIP_TRY(ctx, ensure(&ctx->staging, &ctx->staging_bytes, std::max<size_t>(off, 256)));
+    base = static_cast<char*>(ctx->staging);
+    if (b_x) MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_x, x, b_x, hipMemcpyHostToDevice, ctx->stream));
+    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_vals, values, b_vv, hipMemcpyHostToDevice, ctx->stream));
+    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_mask, fixed_mask, b_mask, hipMemcpyHostToDevice, ctx->stream));
+    if (!with_time) MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_times, times, b_T, hipMemcpyHostToDevice, ctx->stream));
+    if (b_grid) MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_grid, grid->distance, b_grid, hipMemcpyHostToDevice, ctx->stream));
+    if (b_state) MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_state, state, b_state, hipMemcpyHostToDevice, ctx->stream));
+    d_x = reinterpret_cast<const double*>(base + o_x);
+    d_vals = reinterpret_cast<const double*>(base + o_vals);
+    d_mask = reinterpret_cast<const uint8_t*>(base + o_mask);
+    d_times = with_time ? nullptr : reinterpret_cast<const double*>(base + o_times);
+    d_grid = b_grid ? reinterpret_cast<const float*>(base + o_grid) : nullptr;
+    d_state = b_state ? reinterpret_cast<mtg_objective_state*>(base + o_state) : nullptr;
+    d_cost = reinterpret_cast<double*>(base + o_cost);
+    d_grad = with_grad ? reinterpret_cast<double*>(base + o_grad) : nullptr;
+    d_w = b_w ? reinterpret_cast<double*>(base + o_w) : nullptr;
+    d_co = b_co ? reinterpret_cast<uint8_t*>(base + o_co) : nullptr;
+    d_stat = b_stat ? reinterpret_cast<int32_t*>(base + o_stat) : nullptr;
+  }
+
+  // ---- the launches
+  MTG_HIP_TRY(ctx, time_begin(ctx, false));
+  mtg::ObjectiveUnpackArgs ua{d_x, d_vals, d_mask, with_time ? nullptr : d_times, wd(w_vv), wd(w_T), wi(w_nf), wi(w_su),
+                              wd(w_ones), batch, x_stride, K, V, h, D};
+  MTG_HIP_TRY(ctx, mtg::launch_objective_unpack(ua, ctx->stream));
+  // (entries >= n_free of grad_d / grad_c are read by nobody but a caller of the parts)
+  if (with_grad && parts && parts->grad_d) MTG_HIP_TRY(ctx, hipMemsetAsync(wd(w_gd), 0, b_g, ctx->stream));
+  if (with_grad && with_coll && parts && parts->grad_c) MTG_HIP_TRY(ctx, hipMemsetAsync(wd(w_gc), 0, b_g, ctx->stream));
+  MTG_HIP_TRY(ctx, mtg::launch_cost_at_times(N, r, wd(w_vv), d_mask, wd(w_T), wd(w_ones), wd(w_Jd),
+                                             with_grad ? wd(w_gd) : nullptr, batch, K, D, 1, ctx->stream));
+  if (with_coll)
+    MTG_HIP_TRY(ctx, mtg::launch_collision_cost(N, wd(w_vv), d_mask, wd(w_T), *grid, d_grid, *collision, wd(w_Jc),
+                                                with_grad ? wd(w_gc) : nullptr, reinterpret_cast<uint8_t*>(ws + w_coll),
+                                                nullptr, wi(w_sc), batch, K, ctx->stream));
+  const bool soft_grad = with_grad && with_coll;  // objective 0 uses the soft-constraint cost only
+  if (with_soft)
+    MTG_HIP_TRY(ctx, mtg::launch_soft_constraint_cost(N, wd(w_vv), d_mask, wd(w_T), *soft, wd(w_Jsc),
+                                                      soft_grad ? wd(w_gsc) : nullptr, nullptr, wi(w_ss), batch, K, D,
+                                                      ctx->stream));
+  if (with_time && with_grad) {
+    MTG_HIP_TRY(ctx, mtg::launch_time_jacobian(N, r, wd(w_vv), wd(w_T), wd(w_ones), wd(w_Jd2), wd(w_jd),
+                                               params->increment_time, batch, K, D, 1, ctx->stream));
+    MTG_HIP_TRY(ctx, mtg::launch_collision_time_gradient(N, wd(w_vv), wd(w_T), *grid, d_grid, *collision,
+                                                         params->increment_time, wd(w_jc), nullptr, nullptr, nullptr,
+                                                         wi(w_st), batch, K, ctx->stream));
+  }
+  mtg::ObjectiveCombineArgs ca{};
+  ca.J_d = wd(w_Jd);
+  ca.J_c = with_coll ? wd(w_Jc) : nullptr;
+  ca.J_sc = with_soft ? wd(w_Jsc) : nullptr;
+  ca.grad_d = with_grad ? wd(w_gd) : nullptr;
+  ca.grad_c = with_grad && with_coll ? wd(w_gc) : nullptr;
+  ca.grad_sc = soft_grad && with_soft ? wd(w_gsc) : nullptr;
+  ca.dJd_dt = with_time && with_grad ? wd(w_jd) : nullptr;
+  ca.dJc_dt = with_time && with_grad ? wd(w_jc) : nullptr;
+  ca.times = wd(w_T);
+  ca.collision = with_coll ? reinterpret_cast<const uint8_t*>(ws + w_coll) : nullptr;
+  ca.n_free = wi(w_nf);
+  ca.st_unpack = wi(w_su);
+  ca.st_collision = with_coll ? wi(w_sc) : nullptr;
+  ca.st_soft = with_soft ? wi(w_ss) : nullptr;
+  ca.st_collision_time = with_time && with_grad ? wi(w_st) : nullptr;
+  ca.cost_out = d_cost;
+  ca.grad_out = d_grad;
+  ca.weighted = d_w;
+  ca.J_t_out = wd(w_Jt);
+  ca.collision_out = d_co;
+  ca.state = d_state;
+  ca.status = d_stat;
+  ca.B = batch;
+  ca.x_stride = x_stride;
+  ca.K = K, ca.V = V, ca.h = h, ca.D = D;
+  ca.rule = mtg::ObjectiveRule{obj, params->w_d, params->w_c, params->w_t, params->w_sc, params->is_collision_safe,
+                               params->is_coll_raise_first_iter, params->add_coll_raise};
+  MTG_HIP_TRY(ctx, mtg::launch_objective_combine(ca, ctx->stream));
+  MTG_HIP_TRY(ctx, time_end(ctx));
+
+  // ---- the parts (from the workspace) and, for host pointers, the outputs
+  const hipMemcpyKind out_kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (parts) {
+    const struct { double* dst; size_t off, bytes; bool have; } pc[] = {
+        {parts->J_d, w_Jd, b_s, true}, {parts->J_c, w_Jc, b_s, with_coll}, {parts->J_sc, w_Jsc, b_s, with_soft},
+        {parts->J_t, w_Jt, b_s, true}, {parts->dJd_dt, w_jd, b_jt, b_jt != 0}, {parts->dJc_dt, w_jc, b_jt, b_jt != 0},
+        {parts->grad_d, w_gd, b_g, with_grad}, {parts->grad_c, w_gc, b_g, with_grad && with_coll},
+        {parts->grad_sc, w_gsc, b_g, soft_grad && with_soft}};
+    for (const auto& q : pc)
+      if (q.dst && q.have && q.bytes)
+        MTG_HIP_TRY(ctx, hipMemcpyAsync(q.dst, ws + q.off, q.bytes, out_kind, ctx->stream));
+  }
+  if (!dev) {
+    MTG_HIP_TRY(ctx, hipMemcpyAsync(cost_out, base + o_cost, b_s, hipMemcpyDeviceToHost, ctx->stream));
+    if (b_grad) MTG_HIP_TRY(ctx, hipMemcpyAsync(grad_out, base + o_grad, b_grad, hipMemcpyDeviceToHost, ctx->stream));
+    if (b_w) MTG_HIP_TRY(ctx, hipMemcpyAsync(weighted_costs_out, base + o_w, b_w, hipMemcpyDeviceToHost, ctx->stream));
+    if (b_co) MTG_HIP_TRY(ctx, hipMemcpyAsync(collision_out, base + o_co, b_co, hipMemcpyDeviceToHost, ctx->stream));
+    if (b_state) MTG_HIP_TRY(ctx, hipMemcpyAsync(state, base + o_state, b_state, hipMemcpyDeviceToHost, ctx->stream));
+    if (b_stat) MTG_HIP_TRY(ctx, hipMemcpyAsync(status, base + o_stat, b_stat, hipMemcpyDeviceToHost, ctx->stream));
+    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  } else if (!(flags & MTG_FLAG_ASYNC)) {
+    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return MTG_OK;
+}
+
 namespace {
 
 // Shared body of the two vertex <-> coefficient maps: [B][V][h][D] <-> [B][K][D][N].

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "mtg.h"
+#include "mtg_objective_common.h"
 
 namespace mtg {
 
@@ -116,6 +117,38 @@ size_t time_jacobian_lds_bytes(int N, int D, int K, int C);
 hipError_t launch_time_jacobian(int N, int r, const double* values, const double* times, const double* scales,
                                 double* cost, double* jac, double delta, int64_t B, int K, int D, int C,
                                 hipStream_t stream);
+
+// the objective in the optimiser's variables (mtg_objective.hip): the unpack and combine kernels around
+// the component launchers above.  All pointers are device pointers.
+struct ObjectiveUnpackArgs {
+  const double* x;         // [B][x_stride]
+  const double* values;    // [B][V][h][D]
+  const uint8_t* mask;     // [B][V]
+  const double* times_in;  // [B][K], or nullptr: the times lead the rows of x (objective 2)
+  double* vertex_values;   // [B][V][h][D]
+  double* times;           // [B][K]
+  int32_t* n_free;         // [B]
+  int32_t* status;         // [B]: MTG_TRAJ_BAD_TIME, MTG_TRAJ_ROW_TOO_SHORT
+  double* ones;            // [K]: the scales of 1
+  int64_t B, x_stride;
+  int K, V, h, D;
+};
+struct ObjectiveCombineArgs {
+  const double *J_d, *J_c, *J_sc;              // [B] (J_c, J_sc nullable: 0)
+  const double *grad_d, *grad_c, *grad_sc;     // [B][D][V*h] (grad_c, grad_sc nullable: 0)
+  const double *dJd_dt, *dJc_dt, *times;       // [B][K]
+  const uint8_t* collision;                    // [B] (nullable: 0)
+  const int32_t *n_free, *st_unpack, *st_collision, *st_soft, *st_collision_time;  // [B] (st_* nullable)
+  double *cost_out, *grad_out, *weighted, *J_t_out;
+  uint8_t* collision_out;
+  mtg_objective_state* state;
+  int32_t* status;
+  int64_t B, x_stride;
+  int K, V, h, D;
+  ObjectiveRule rule;
+};
+hipError_t launch_objective_unpack(const ObjectiveUnpackArgs& a, hipStream_t stream);
+hipError_t launch_objective_combine(const ObjectiveCombineArgs& a, hipStream_t stream);
 
 // vertex derivatives <-> coefficients (mtg_vertex.hip)
 bool vertex_map_fits(int N, int D, int K);

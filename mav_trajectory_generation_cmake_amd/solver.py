@@ -355,6 +355,23 @@ class Context:
         return {"J_t": times.sum(1), "grad_t": (w_d * jd + w_c * c["grad_t"]) + w_t, "dJd_dt": jd, "dJc_dt": c["grad_t"],
                 "status": c["status"]}
 
+    def objective_batch(self, N, values, mask, x, params, times=None, grid=None, collision=None, soft=None, state=None,
+                        grad=True, parts=False, asynchronous=False):
+        """One evaluation of the reference's nonlinear objective per trajectory, in the optimiser's variables
+        (include/mtg.h mtg_objective_batch): x [B][x_stride] holds (objective 2: the K segment times, then)
+        D blocks of n_free[b] free derivatives; values / mask are the problem as solve_linear_batch reads
+        it; params an ObjectiveParams; times [B][K] for objectives 0 and 1; grid / collision (SdfGrid,
+        CollisionParams) for objectives 1 and 2; soft a SoftConstraintParams iff
+        params.use_soft_constraints.  numpy arrays (staged once) or torch CUDA tensors (then grid.distance
+        and state are tensors too, the launches go to torch's current stream and asynchronous=True does
+        not wait for them).  state (optional, in/out): OBJECTIVE_STATE_DTYPE [B], or a torch uint8 tensor
+        [B][48] holding the same records.  Returns dict(cost [B], grad [B][x_stride] or None,
+        weighted_costs [B][4], collision [B] uint8, status [B] int32, state) and with parts=True the
+        unweighted parts J_d, J_c, J_sc, J_t, dJd_dt, dJc_dt, grad_d, grad_c, grad_sc (None where the
+        objective does not compute one)."""
+        return _objective_call(self, N, values, mask, x, params, times, grid, collision, soft, state, grad, parts,
+                               asynchronous, None)
+
     def soft_constraint_cost_batch(self, N, vertex_values, times, params, mask=None, grad=False, asynchronous=False):
         """getCostAndGradientSoftConstraints for a batch (include/mtg.h mtg_soft_constraint_cost_batch):
         vertex_values [B][V][h][D] (all derivatives), times [B][K], params a SoftConstraintParams.  numpy
@@ -782,6 +799,175 @@ def host_soft_constraint_cost_batch(N, vertex_values, times, params, mask=None, 
                                                       _addr(out["grad"]), _addr(out["maxima"]), _addr(out["status"]),
                                                       threads))
     return out
+
+
+# struct mtg_objective_state (include/mtg.h); all-zero = a fresh optimisation
+OBJECTIVE_STATE_DTYPE = np.dtype([("total_cost_iter0", "<f8"), ("cost_trajectory", "<f8"), ("cost_collision", "<f8"),
+                                  ("cost_time", "<f8"), ("cost_soft_constraints", "<f8"), ("n_iterations", "<i4"),
+                                  ("iter0_done", "<i4")])
+
+OBJECTIVE_PARTS = ("J_d", "J_c", "J_sc", "J_t", "dJd_dt", "dJc_dt", "grad_d", "grad_c", "grad_sc")
+
+
+class ObjectiveParams:
+    """struct mtg_objective_params (include/mtg.h): which of the reference's objective functions
+    (0 free constraints, 1 + collision, 2 + collision + time), the weights w_d, w_c, w_t, w_sc (reference
+    defaults 0.1, 10, 1, 1), increment_time, and the "raise the cost while in collision" switches."""
+
+    def __init__(self, objective, derivative_to_optimize, w_d=0.1, w_c=10.0, w_t=1.0, w_sc=1.0, increment_time=0.1,
+                 use_soft_constraints=True, is_collision_safe=False, is_coll_raise_first_iter=True, add_coll_raise=0.0,
+                 reserved=0):
+        self.objective = int(objective)
+        self.derivative_to_optimize = int(derivative_to_optimize)
+        self.w_d, self.w_c, self.w_t, self.w_sc = float(w_d), float(w_c), float(w_t), float(w_sc)
+        self.increment_time = float(increment_time)
+        self.use_soft_constraints = bool(use_soft_constraints)
+        self.is_collision_safe = bool(is_collision_safe)
+        self.is_coll_raise_first_iter = bool(is_coll_raise_first_iter)
+        self.add_coll_raise = float(add_coll_raise)
+        self.reserved = int(reserved)
+
+    def native(self):
+        return nat.ObjectiveParams(self.objective, self.derivative_to_optimize, self.w_d, self.w_c, self.w_t, self.w_sc,
+                                   self.increment_time, int(self.use_soft_constraints), int(self.is_collision_safe),
+                                   int(self.is_coll_raise_first_iter), self.reserved, self.add_coll_raise)
+
+
+def number_of_free_constraints(mask, N):
+    """n_free [B]: the derivatives below N/2 that mask [B][V] does not fix (bit 7 and bits >= N/2 ignored)."""
+    h = N // 2
+    m = np.asarray(mask).astype(np.uint32)
+    return (h - ((m[:, :, None] >> np.arange(h)[None, None, :]) & 1).sum(axis=2)).sum(axis=1).astype(np.int32)
+
+
+def pack_optimization_variables(times, free, n_free, x_stride=None):
+    """x [B][x_stride] in the layout of objective_batch: times [B][K] (or None: objectives 0 and 1), then
+    for each of the D dimensions the first n_free[b] entries of free [B][D][*].  x_stride defaults to
+    the longest row; the padding is 0."""
+    free = np.asarray(free, dtype=np.float64)
+    B, D = free.shape[0], free.shape[1]
+    n_free = np.asarray(n_free)
+    K = 0 if times is None else np.asarray(times).shape[1]
+    longest = K + D * int(n_free.max()) if B else K
+    stride = longest if x_stride is None else int(x_stride)
+    assert stride >= longest, "x_stride is shorter than the longest row"
+    x = np.zeros((B, stride))
+    for b in range(B):
+        nf = int(n_free[b])
+        if K:
+            x[b, :K] = np.asarray(times)[b]
+        for d in range(D):
+            x[b, K + d * nf:K + (d + 1) * nf] = free[b, d, :nf]
+    return x
+
+
+def unpack_optimization_variables(x, n_free, D, n_times=0, width=None):
+    """The inverse of pack_optimization_variables: (times [B][n_times] or None, free [B][D][width]) with
+    the entries past n_free[b] zero; width defaults to the largest n_free."""
+    x = np.asarray(x, dtype=np.float64)
+    n_free = np.asarray(n_free)
+    B = x.shape[0]
+    width = int(n_free.max()) if width is None and B else int(width or 0)
+    free = np.zeros((B, D, width))
+    for b in range(B):
+        nf = int(n_free[b])
+        for d in range(D):
+            free[b, d, :nf] = x[b, n_times + d * nf:n_times + (d + 1) * nf]
+    return (x[:, :n_times].copy() if n_times else None), free
+
+
+def _objective_call(ctx, N, values, mask, x, params, times, grid, collision, soft, state, grad, parts, asynchronous,
+                    threads):
+    """Shared body of Context.objective_batch (ctx given) and host_objective_batch (ctx None)."""
+    lib = nat.load()
+    dev = ctx is not None and _is_torch(x) and x.is_cuda
+    B, V, h, D = values.shape
+    K = V - 1
+    assert h == N // 2 and tuple(mask.shape) == (B, V) and x.shape[0] == B and len(x.shape) == 2
+    stride = int(x.shape[1])
+    p = params.native()
+    with_coll, with_time, with_soft = p.objective >= 1, p.objective == 2, bool(p.use_soft_constraints)
+    shapes = {"J_d": (B,), "J_c": (B,), "J_sc": (B,), "J_t": (B,), "dJd_dt": (B, K), "dJc_dt": (B, K),
+              "grad_d": (B, D, V * h), "grad_c": (B, D, V * h), "grad_sc": (B, D, V * h)}
+    have = {"J_d": True, "J_c": with_coll, "J_sc": with_soft, "J_t": True, "dJd_dt": grad and with_time,
+            "dJc_dt": grad and with_time, "grad_d": grad, "grad_c": grad and with_coll,
+            "grad_sc": grad and with_coll and with_soft}
+    if dev:
+        import torch
+        kw = dict(device=x.device)
+        assert grid is None or (_is_torch(grid.distance) and grid.distance.is_cuda), \
+            "device call: grid.distance must be a CUDA tensor"
+        assert x.is_contiguous() and values.is_contiguous() and mask.is_contiguous()
+
+        def new(shape, dtype="f8"):
+            return torch.zeros(shape, dtype={"f8": torch.float64, "u1": torch.uint8, "i4": torch.int32}[dtype], **kw)
+        flags = nat.MTG_FLAG_DEVICE_PTRS | (nat.MTG_FLAG_ASYNC if asynchronous else 0)
+        ctx.set_stream(torch.cuda.current_stream(x.device).cuda_stream)
+    else:
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        times = np.ascontiguousarray(times, dtype=np.float64) if times is not None else None
+        if state is not None:
+            assert state.dtype == OBJECTIVE_STATE_DTYPE and state.flags.c_contiguous and state.shape == (B,)
+
+        def new(shape, dtype="f8"):
+            return np.zeros(shape, dtype={"f8": np.float64, "u1": np.uint8, "i4": np.int32}[dtype])
+        flags = 0
+        if ctx is not None:
+            ctx.reset_stream()
+    assert times is None or tuple(times.shape) == (B, K)
+    out = {"cost": new((B,)), "grad": new((B, stride)) if grad else None, "weighted_costs": new((B, 4)),
+           "collision": new((B,), "u1"), "status": new((B,), "i4"), "state": state}
+    for k in OBJECTIVE_PARTS:
+        out[k] = new(shapes[k]) if parts and have[k] else None
+    pp = nat.ObjectiveParts(*[_addr(out[k]) for k in OBJECTIVE_PARTS])
+    g, keep = grid.native() if grid is not None else (None, None)
+    cp = collision.native() if collision is not None else None
+    sp = soft.native() if soft is not None else None
+    tail = (_addr(x), stride, ctypes.byref(p), ctypes.byref(g) if g is not None else None,
+            ctypes.byref(cp) if cp is not None else None, ctypes.byref(sp) if sp is not None else None,
+            _addr(out["cost"]), _addr(out["grad"]), _addr(out["weighted_costs"]), _addr(out["collision"]), _addr(state),
+            ctypes.byref(pp) if parts else None, _addr(out["status"]))
+    if ctx is not None:
+        nat.check(lib.mtg_objective_batch(ctx.handle, N, D, K, B, _addr(values), _addr(mask), _addr(times), *tail,
+                                          flags), ctx.handle)
+    else:
+        nat.check(lib.mtg_host_objective_batch(N, D, K, B, _addr(values), _addr(mask), _addr(times), *tail, threads))
+    del keep
+    return out
+
+
+def host_objective_batch(N, values, mask, x, params, times=None, grid=None, collision=None, soft=None, state=None,
+                         grad=True, parts=False, threads=1):
+    """The library's host path of Context.objective_batch (mtg_host_objective_batch), no GPU: same
+    arguments (numpy arrays) and outputs."""
+    return _objective_call(None, N, values, mask, x, params, times, grid, collision, soft, state, grad, parts, False,
+                           threads)
+
+
+def host_objective_bounds_batch(N, D, K, mask, x, derivative_to_optimize, with_times, solve_with_position_constraint,
+                                constraints=None, min_bound=None, max_bound=None, initial_stepsize_rel=0.1):
+    """Bounds and initial step of the optimiser's variables (mtg_host_objective_bounds_batch: the reference's
+    setFreeEndpointDerivativeHardConstraints and the time bounds / initial step of its optimize set-up,
+    restated literally).  mask [B][V], x [B][x_stride] in objective_batch's layout (with the K times first
+    when with_times), constraints a SoftConstraintParams (its (derivative, limit) pairs) or None,
+    min_bound / max_bound [D] (needed without the position constraint).  Returns (lower, upper,
+    initial_step), each [B][x_stride]; raises MTGError(MTG_ERR_INVALID_ARGUMENT) where the reference's
+    index runs past the end."""
+    mask = np.ascontiguousarray(mask, dtype=np.uint8)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    B, stride = x.shape
+    assert mask.shape == (B, K + 1)
+    lo, up, step = np.zeros((B, stride)), np.zeros((B, stride)), np.zeros((B, stride))
+    mn = np.ascontiguousarray(min_bound, dtype=np.float64) if min_bound is not None else None
+    mx = np.ascontiguousarray(max_bound, dtype=np.float64) if max_bound is not None else None
+    cp = constraints.native() if constraints is not None else None
+    nat.check(nat.load().mtg_host_objective_bounds_batch(
+        N, D, K, B, _addr(mask), int(bool(with_times)), _addr(x), stride, int(derivative_to_optimize),
+        int(bool(solve_with_position_constraint)), ctypes.byref(cp) if cp is not None else None, _addr(mn), _addr(mx),
+        float(initial_stepsize_rel), _addr(lo), _addr(up), _addr(step)))
+    return lo, up, step
 
 
 def host_min_max_magnitude_batch(coeffs, times, derivative, dimensions=None, threads=1):
