@@ -140,6 +140,8 @@ int set_error(mtg_ctx* ctx, int code, const char* what) {
 
 size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
 
+size_t grid_bytes(const mtg_sdf_grid& g) { return sizeof(float) * (size_t)g.nx * g.ny * g.nz; }
+
 // host-pointer calls whose staged arrays fit this size go through one pinned buffer
 constexpr size_t kPinnedMax = 1u << 20;
 
@@ -155,6 +157,90 @@ hipError_t ensure(void** buf, size_t* have, size_t need) {
   if (e == hipSuccess) *have = need;
   return e;
 }
+
+// The arrays of one call.  Each array is registered once, with the pointer the launch will use:
+// *dev is the caller's pointer at once, and stays so in a device-pointer call (MTG_FLAG_DEVICE_PTRS),
+// also where 0 bytes are registered.  In a host-pointer call upload() gives every array with bytes and
+// a host pointer a 256-B aligned slot of ctx->staging (inputs first, each group in registration
+// order), sizes the buffer, and only then points *dev into it (nullptr for the others) and queues the
+// H2D copy of each input; finish() queues the D2H copy of each output and waits for the stream.  A
+// device-pointer call's finish() waits unless MTG_FLAG_ASYNC.  Everything goes on ctx->stream; the
+// memsets, the timed region and the launches stay with the caller, between the two.  Both return an
+// MTG_* code with mtg_last_error set.
+class Staged {
+ public:
+  Staged(mtg_ctx* ctx, unsigned flags) : ctx_(ctx), dev_(flags & MTG_FLAG_DEVICE_PTRS), async_(flags & MTG_FLAG_ASYNC) {}
+  template <class T>
+  void in(const T** dev, const T* host, size_t bytes) {
+    *dev = host;
+    add(dev, const_cast<T*>(host), bytes, kIn);
+  }
+  template <class T>
+  void out(T** dev, T* host, size_t bytes) {
+    *dev = host;
+    add(dev, host, bytes, kOut);
+  }
+  template <class T>
+  void inout(T** dev, T* host, size_t bytes) {
+    *dev = host;
+    add(dev, host, bytes, kIn | kOut);
+  }
+
+  int upload() {
+    if (overflow_) return set_error(ctx_, MTG_ERR_INVALID_ARGUMENT, "internal: a call stages more arrays than Staged holds");
+    if (dev_) return MTG_OK;
+    size_t off = 0;
+    for (unsigned pass : {kIn, 0u})
+      for (int i = 0; i < n_; ++i)
+        if ((rec_[i].dir & kIn) == pass) {
+          rec_[i].off = off;
+          off = align_up(off + rec_[i].bytes);
+        }
+    hipError_t e = ensure(&ctx_->staging, &ctx_->staging_bytes, std::max<size_t>(off, 256));
+    if (e != hipSuccess) return set_hip_error(ctx_, e, "stage inputs: ensure(staging)");
+    for (int i = 0; i < n_; ++i) {
+      const Rec& r = rec_[i];
+      void* p = r.bytes ? static_cast<char*>(ctx_->staging) + r.off : nullptr;
+      std::memcpy(r.dev, &p, sizeof(p));  // (every *dev is an object pointer)
+      if (r.bytes && (r.dir & kIn)) {
+        e = hipMemcpyAsync(p, r.host, r.bytes, hipMemcpyHostToDevice, ctx_->stream);
+        if (e != hipSuccess) return set_hip_error(ctx_, e, "stage inputs");
+      }
+    }
+    return MTG_OK;
+  }
+
+  int finish() {
+    if (dev_ && async_) return MTG_OK;
+    for (int i = 0; !dev_ && i < n_; ++i) {
+      const Rec& r = rec_[i];
+      if (!r.bytes || !(r.dir & kOut)) continue;
+      hipError_t e = hipMemcpyAsync(r.host, static_cast<char*>(ctx_->staging) + r.off, r.bytes, hipMemcpyDeviceToHost,
+                                    ctx_->stream);
+      if (e != hipSuccess) return set_hip_error(ctx_, e, "copy outputs");
+    }
+    MTG_HIP_TRY(ctx_, hipStreamSynchronize(ctx_->stream));
+    return MTG_OK;
+  }
+
+ private:
+  static constexpr unsigned kIn = 1, kOut = 2;
+  static constexpr int kMax = 16;  // (the objective stages 11)
+  struct Rec {
+    void* dev;   // the caller's T* variable
+    void* host;
+    size_t bytes, off;
+    unsigned dir;
+  };
+  void add(void* dev, void* host, size_t bytes, unsigned dir) {
+    if (n_ < kMax) rec_[n_++] = Rec{dev, host, host ? bytes : 0, 0, dir};
+    else overflow_ = true;  // upload() reports it
+  }
+  mtg_ctx* ctx_;
+  bool dev_, async_, overflow_ = false;
+  int n_ = 0;
+  Rec rec_[kMax];
+};
 
 // Timed region around one launch.  single: the call launches exactly one kernel through
 // mtg::launch_kernel, which carries the event pair in its dispatch packet; otherwise (the split
@@ -214,12 +300,50 @@ hipError_t create_events(mtg_ctx* ctx, int ring) {
   return hipSuccess;
 }
 
+// The argument checks that several entries make.  Each returns MTG_OK or the entry's return code with
+// mtg_last_error set; an entry calls them in the order it reports its errors.
+int check_order(mtg_ctx* ctx, int N) {
+  if (N < 2 || N > 12 || (N % 2)) return set_error(ctx, MTG_ERR_UNSUPPORTED_N, "N must be even and in [2, 12]");
+  return MTG_OK;
+}
+
+int check_dims(mtg_ctx* ctx, int D, int K, int64_t batch) {
+  if (K < 1 || D < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need K >= 1, D >= 1, batch >= 0");
+  return MTG_OK;
+}
+
+// the collision term's shape, grid and parameters; missing: the text for an absent grid or params
+int check_collision(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const mtg_sdf_grid* grid,
+                    const mtg_collision_params* params, const char* missing = "grid and params are required") {
+  if (N < 6 || N > 12 || (N % 2)) return set_error(ctx, MTG_ERR_UNSUPPORTED_N, "N must be 6, 8, 10 or 12");
+  if (D != 3) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "the collision term needs D == 3");
+  if (K < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need K >= 1, batch >= 0");
+  if (!grid || !params) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, missing);
+  if (!(params->coll_check_time_increment > 0.0) || !(params->map_resolution >= 0.0) || !(grid->resolution > 0.0) ||
+      grid->nx < 1 || grid->ny < 1 || grid->nz < 1)
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT,
+                     "need coll_check_time_increment > 0, map_resolution >= 0, grid resolution > 0, grid dimensions >= 1");
+  return MTG_OK;
+}
+
+// the soft-constraint parameters; count_text: the text for absent params or n_constraints out of [1, 8]
+int check_soft_params(mtg_ctx* ctx, int N, const mtg_soft_constraint_params* p, const char* count_text) {
+  if (!p || p->n_constraints < 1 || p->n_constraints > 8) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, count_text);
+  const int kmax = N - 2 < 4 ? N - 2 : 4;
+  for (int c = 0; c < p->n_constraints; ++c)
+    if (p->derivative[c] < 0 || p->derivative[c] > kmax || !(p->limit[c] > 0.0))
+      return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "need 0 <= derivative <= min(4, N - 2) and limit > 0");
+  return MTG_OK;
+}
+
 int check_shape(mtg_ctx* ctx, int N, int D, int K, int r, int64_t batch) {
   if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
-  if (N < 2 || N > 12 || (N % 2)) return set_error(ctx, MTG_ERR_UNSUPPORTED_N, "N must be even and in [2, 12]");
+  int rc = check_order(ctx, N);
+  if (rc != MTG_OK) return rc;
   if (r < 0 || r > N / 2 - 1)
     return set_error(ctx, MTG_ERR_BAD_DERIVATIVE, "derivative_to_optimize must be in [0, N/2-1]");
-  if (K < 1 || D < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need K >= 1, D >= 1, batch >= 0");
+  rc = check_dims(ctx, D, K, batch);
+  if (rc != MTG_OK) return rc;
   int lg, tpb;
   size_t lds;
   if (!mtg::solve_geometry(N, D, K, &lg, &lds, &tpb))
@@ -888,51 +1012,24 @@ int mtg_cost_at_times_batch(mtg_ctx* ctx, int N, int D, int K, int derivative_to
   std::lock_guard<std::mutex> g(ctx->mu);
   MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int V = K + 1, h = N / 2, C = n_candidates;
-  const size_t b_vals = sizeof(double) * (size_t)batch * V * h * D, b_mask = grad_out ? (size_t)batch * V : 0,
-               b_times = sizeof(double) * (size_t)batch * K, b_scales = sizeof(double) * (size_t)C * K,
-               b_cost = sizeof(double) * (size_t)batch * C,
-               b_grad = grad_out ? sizeof(double) * (size_t)batch * C * D * V * h : 0;
-  const double* d_vals = vertex_values;
-  const uint8_t* d_mask = fixed_mask;
-  const double *d_times = times, *d_scales = scales;
-  double *d_cost = cost_out, *d_grad = grad_out;
-  const bool dev = flags & MTG_FLAG_DEVICE_PTRS;
-  char* base = nullptr;
-  size_t o_cost = 0, o_grad = 0;
-  if (!dev) {
-    size_t off = 0;
-    const size_t o_vals = off; off = align_up(off + b_vals);
-    const size_t o_mask = off; off = align_up(off + b_mask);
-    const size_t o_times = off; off = align_up(off + b_times);
-    const size_t o_scales = off; off = align_up(off + b_scales);
-    o_cost = off; off = align_up(off + b_cost);
-    o_grad = off; off = align_up(off + b_grad);
-    MTG_HIP_TRY(ctx, ensure(&ctx->staging, &ctx->staging_bytes, std::max<size_t>(off, 256)));
-    base = static_cast<char*>(ctx->staging);
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_vals, vertex_values, b_vals, hipMemcpyHostToDevice, ctx->stream));
-    if (b_mask) MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_mask, fixed_mask, b_mask, hipMemcpyHostToDevice, ctx->stream));
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_times, times, b_times, hipMemcpyHostToDevice, ctx->stream));
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_scales, scales, b_scales, hipMemcpyHostToDevice, ctx->stream));
-    d_vals = reinterpret_cast<const double*>(base + o_vals);
-    d_mask = b_mask ? reinterpret_cast<const uint8_t*>(base + o_mask) : nullptr;
-    d_times = reinterpret_cast<const double*>(base + o_times);
-    d_scales = reinterpret_cast<const double*>(base + o_scales);
-    d_cost = reinterpret_cast<double*>(base + o_cost);
-    d_grad = grad_out ? reinterpret_cast<double*>(base + o_grad) : nullptr;
-  }
+  const size_t nB = (size_t)batch, b_grad = sizeof(double) * nB * C * D * V * h;
+  const double *d_vals, *d_times, *d_scales;
+  const uint8_t* d_mask;
+  double *d_cost, *d_grad;
+  Staged st(ctx, flags);
+  st.in(&d_vals, vertex_values, sizeof(double) * nB * V * h * D);
+  st.in(&d_mask, fixed_mask, grad_out ? nB * V : 0);
+  st.in(&d_times, times, sizeof(double) * nB * K);
+  st.in(&d_scales, scales, sizeof(double) * (size_t)C * K);
+  st.out(&d_cost, cost_out, sizeof(double) * nB * C);
+  st.out(&d_grad, grad_out, b_grad);
+  if (int rc = st.upload()) return rc;
   if (d_grad) MTG_HIP_TRY(ctx, hipMemsetAsync(d_grad, 0, b_grad, ctx->stream));
   MTG_HIP_TRY(ctx, time_begin(ctx));
   MTG_HIP_TRY(ctx, mtg::launch_cost_at_times(N, derivative_to_optimize, d_vals, d_mask, d_times, d_scales, d_cost,
                                              d_grad, batch, K, D, C, ctx->stream));
   MTG_HIP_TRY(ctx, time_end(ctx));
-  if (!dev) {
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(cost_out, base + o_cost, b_cost, hipMemcpyDeviceToHost, ctx->stream));
-    if (grad_out) MTG_HIP_TRY(ctx, hipMemcpyAsync(grad_out, base + o_grad, b_grad, hipMemcpyDeviceToHost, ctx->stream));
-    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  } else if (!(flags & MTG_FLAG_ASYNC)) {
-    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return MTG_OK;
+  return st.finish();
 }
 
 int mtg_collision_cost_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* vertex_values,
@@ -940,14 +1037,7 @@ int mtg_collision_cost_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, c
                              const mtg_collision_params* params, double* cost_out, double* grad_out,
                              uint8_t* collision_out, int32_t* n_evaluated_out, int32_t* status, unsigned flags) {
   if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
-  if (N < 6 || N > 12 || (N % 2)) return set_error(ctx, MTG_ERR_UNSUPPORTED_N, "N must be 6, 8, 10 or 12");
-  if (D != 3) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "the collision term needs D == 3");
-  if (K < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need K >= 1, batch >= 0");
-  if (!grid || !params) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "grid and params are required");
-  if (!(params->coll_check_time_increment > 0.0) || !(params->map_resolution >= 0.0) || !(grid->resolution > 0.0) ||
-      grid->nx < 1 || grid->ny < 1 || grid->nz < 1)
-    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT,
-                     "need coll_check_time_increment > 0, map_resolution >= 0, grid resolution > 0, grid dimensions >= 1");
+  if (int rc = check_collision(ctx, N, D, K, batch, grid, params)) return rc;
   if (batch == 0) return MTG_OK;
   if (!vertex_values || !times || !cost_out || !grid->distance || (grad_out && !fixed_mask))
     return set_error(ctx, MTG_ERR_INVALID_ARGUMENT,
@@ -957,64 +1047,30 @@ int mtg_collision_cost_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, c
   std::lock_guard<std::mutex> g(ctx->mu);
   MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int V = K + 1, h = N / 2;
-  const size_t b_vals = sizeof(double) * (size_t)batch * V * h * D, b_mask = grad_out ? (size_t)batch * V : 0,
-               b_times = sizeof(double) * (size_t)batch * K,
-               b_grid = sizeof(float) * (size_t)grid->nx * grid->ny * grid->nz, b_cost = sizeof(double) * (size_t)batch,
-               b_grad = grad_out ? sizeof(double) * (size_t)batch * D * V * h : 0,
-               b_coll = collision_out ? (size_t)batch : 0, b_nev = n_evaluated_out ? sizeof(int32_t) * (size_t)batch : 0,
-               b_stat = status ? sizeof(int32_t) * (size_t)batch : 0;
-  const double *d_vals = vertex_values, *d_times = times;
-  const uint8_t* d_mask = fixed_mask;
-  const float* d_grid = grid->distance;
-  double *d_cost = cost_out, *d_grad = grad_out;
-  uint8_t* d_coll = collision_out;
-  int32_t *d_nev = n_evaluated_out, *d_stat = status;
-  const bool dev = flags & MTG_FLAG_DEVICE_PTRS;
-  char* base = nullptr;
-  size_t o_cost = 0, o_grad = 0, o_coll = 0, o_nev = 0, o_stat = 0;
-  if (!dev) {
-    size_t off = 0;
-    const size_t o_vals = off; off = align_up(off + b_vals);
-    const size_t o_mask = off; off = align_up(off + b_mask);
-    const size_t o_times = off; off = align_up(off + b_times);
-    const size_t o_grid = off; off = align_up(off + b_grid);
-    o_cost = off; off = align_up(off + b_cost);
-    o_grad = off; off = align_up(off + b_grad);
-    o_coll = off; off = align_up(off + b_coll);
-    o_nev = off; off = align_up(off + b_nev);
-    o_stat = off; off = align_up(off + b_stat);
-    MTG_HIP_TRY(ctx, ensure(&ctx->staging, &ctx->staging_bytes, std::max<size_t>(off, 256)));
-    base = static_cast<char*>(ctx->staging);
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_vals, vertex_values, b_vals, hipMemcpyHostToDevice, ctx->stream));
-    if (b_mask) MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_mask, fixed_mask, b_mask, hipMemcpyHostToDevice, ctx->stream));
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_times, times, b_times, hipMemcpyHostToDevice, ctx->stream));
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_grid, grid->distance, b_grid, hipMemcpyHostToDevice, ctx->stream));
-    d_vals = reinterpret_cast<const double*>(base + o_vals);
-    d_mask = b_mask ? reinterpret_cast<const uint8_t*>(base + o_mask) : nullptr;
-    d_times = reinterpret_cast<const double*>(base + o_times);
-    d_grid = reinterpret_cast<const float*>(base + o_grid);
-    d_cost = reinterpret_cast<double*>(base + o_cost);
-    d_grad = grad_out ? reinterpret_cast<double*>(base + o_grad) : nullptr;
-    d_coll = collision_out ? reinterpret_cast<uint8_t*>(base + o_coll) : nullptr;
-    d_nev = n_evaluated_out ? reinterpret_cast<int32_t*>(base + o_nev) : nullptr;
-    d_stat = status ? reinterpret_cast<int32_t*>(base + o_stat) : nullptr;
-  }
+  const size_t nB = (size_t)batch, b_grad = sizeof(double) * nB * D * V * h;
+  const double *d_vals, *d_times;
+  const uint8_t* d_mask;
+  const float* d_grid;
+  double *d_cost, *d_grad;
+  uint8_t* d_coll;
+  int32_t *d_nev, *d_stat;
+  Staged st(ctx, flags);
+  st.in(&d_vals, vertex_values, sizeof(double) * nB * V * h * D);
+  st.in(&d_mask, fixed_mask, grad_out ? nB * V : 0);
+  st.in(&d_times, times, sizeof(double) * nB * K);
+  st.in(&d_grid, grid->distance, grid_bytes(*grid));
+  st.out(&d_cost, cost_out, sizeof(double) * nB);
+  st.out(&d_grad, grad_out, b_grad);
+  st.out(&d_coll, collision_out, nB);
+  st.out(&d_nev, n_evaluated_out, sizeof(int32_t) * nB);
+  st.out(&d_stat, status, sizeof(int32_t) * nB);
+  if (int rc = st.upload()) return rc;
   if (d_grad) MTG_HIP_TRY(ctx, hipMemsetAsync(d_grad, 0, b_grad, ctx->stream));
   MTG_HIP_TRY(ctx, time_begin(ctx));
   MTG_HIP_TRY(ctx, mtg::launch_collision_cost(N, d_vals, d_mask, d_times, *grid, d_grid, *params, d_cost, d_grad, d_coll,
                                               d_nev, d_stat, batch, K, ctx->stream));
   MTG_HIP_TRY(ctx, time_end(ctx));
-  if (!dev) {
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(cost_out, base + o_cost, b_cost, hipMemcpyDeviceToHost, ctx->stream));
-    if (grad_out) MTG_HIP_TRY(ctx, hipMemcpyAsync(grad_out, base + o_grad, b_grad, hipMemcpyDeviceToHost, ctx->stream));
-    if (b_coll) MTG_HIP_TRY(ctx, hipMemcpyAsync(collision_out, base + o_coll, b_coll, hipMemcpyDeviceToHost, ctx->stream));
-    if (b_nev) MTG_HIP_TRY(ctx, hipMemcpyAsync(n_evaluated_out, base + o_nev, b_nev, hipMemcpyDeviceToHost, ctx->stream));
-    if (b_stat) MTG_HIP_TRY(ctx, hipMemcpyAsync(status, base + o_stat, b_stat, hipMemcpyDeviceToHost, ctx->stream));
-    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  } else if (!(flags & MTG_FLAG_ASYNC)) {
-    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return MTG_OK;
+  return st.finish();
 }
 
 int mtg_collision_time_gradient_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* vertex_values,
@@ -1023,14 +1079,7 @@ int mtg_collision_time_gradient_batch(mtg_ctx* ctx, int N, int D, int K, int64_t
                                       int32_t* side_evaluated_out, int32_t* segments_walked_out, int32_t* status,
                                       unsigned flags) {
   if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
-  if (N < 6 || N > 12 || (N % 2)) return set_error(ctx, MTG_ERR_UNSUPPORTED_N, "N must be 6, 8, 10 or 12");
-  if (D != 3) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "the collision term needs D == 3");
-  if (K < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need K >= 1, batch >= 0");
-  if (!grid || !params) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "grid and params are required");
-  if (!(params->coll_check_time_increment > 0.0) || !(params->map_resolution >= 0.0) || !(grid->resolution > 0.0) ||
-      grid->nx < 1 || grid->ny < 1 || grid->nz < 1)
-    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT,
-                     "need coll_check_time_increment > 0, map_resolution >= 0, grid resolution > 0, grid dimensions >= 1");
+  if (int rc = check_collision(ctx, N, D, K, batch, grid, params)) return rc;
   if (!(increment_time > 0.0 && increment_time <= DBL_MAX))
     return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "increment_time must be > 0 and finite");
   if (batch == 0) return MTG_OK;
@@ -1041,58 +1090,26 @@ int mtg_collision_time_gradient_batch(mtg_ctx* ctx, int N, int D, int K, int64_t
   std::lock_guard<std::mutex> g(ctx->mu);
   MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int V = K + 1, h = N / 2;
-  const size_t b_vals = sizeof(double) * (size_t)batch * V * h * D, b_times = sizeof(double) * (size_t)batch * K,
-               b_grid = sizeof(float) * (size_t)grid->nx * grid->ny * grid->nz, b_grad = sizeof(double) * (size_t)batch * K,
-               b_sc = side_cost_out ? sizeof(double) * (size_t)batch * K * 2 : 0,
-               b_se = side_evaluated_out ? sizeof(int32_t) * (size_t)batch * K * 2 : 0,
-               b_wk = segments_walked_out ? sizeof(int32_t) * (size_t)batch : 0,
-               b_stat = status ? sizeof(int32_t) * (size_t)batch : 0;
-  const double *d_vals = vertex_values, *d_times = times;
-  const float* d_grid = grid->distance;
-  double *d_grad = grad_t_out, *d_sc = side_cost_out;
-  int32_t *d_se = side_evaluated_out, *d_wk = segments_walked_out, *d_stat = status;
-  const bool dev = flags & MTG_FLAG_DEVICE_PTRS;
-  char* base = nullptr;
-  size_t o_grad = 0, o_sc = 0, o_se = 0, o_wk = 0, o_stat = 0;
-  if (!dev) {
-    size_t off = 0;
-    const size_t o_vals = off; off = align_up(off + b_vals);
-    const size_t o_times = off; off = align_up(off + b_times);
-    const size_t o_grid = off; off = align_up(off + b_grid);
-    o_grad = off; off = align_up(off + b_grad);
-    o_sc = off; off = align_up(off + b_sc);
-    o_se = off; off = align_up(off + b_se);
-    o_wk = off; off = align_up(off + b_wk);
-    o_stat = off; off = align_up(off + b_stat);
-    MTG_HIP_TRY(ctx, ensure(&ctx->staging, &ctx->staging_bytes, std::max<size_t>(off, 256)));
-    base = static_cast<char*>(ctx->staging);
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_vals, vertex_values, b_vals, hipMemcpyHostToDevice, ctx->stream));
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_times, times, b_times, hipMemcpyHostToDevice, ctx->stream));
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_grid, grid->distance, b_grid, hipMemcpyHostToDevice, ctx->stream));
-    d_vals = reinterpret_cast<const double*>(base + o_vals);
-    d_times = reinterpret_cast<const double*>(base + o_times);
-    d_grid = reinterpret_cast<const float*>(base + o_grid);
-    d_grad = reinterpret_cast<double*>(base + o_grad);
-    d_sc = b_sc ? reinterpret_cast<double*>(base + o_sc) : nullptr;
-    d_se = b_se ? reinterpret_cast<int32_t*>(base + o_se) : nullptr;
-    d_wk = b_wk ? reinterpret_cast<int32_t*>(base + o_wk) : nullptr;
-    d_stat = b_stat ? reinterpret_cast<int32_t*>(base + o_stat) : nullptr;
-  }
+  const size_t nB = (size_t)batch;
+  const double *d_vals, *d_times;
+  const float* d_grid;
+  double *d_grad, *d_sc;
+  int32_t *d_se, *d_wk, *d_stat;
+  Staged st(ctx, flags);
+  st.in(&d_vals, vertex_values, sizeof(double) * nB * V * h * D);
+  st.in(&d_times, times, sizeof(double) * nB * K);
+  st.in(&d_grid, grid->distance, grid_bytes(*grid));
+  st.out(&d_grad, grad_t_out, sizeof(double) * nB * K);
+  st.out(&d_sc, side_cost_out, sizeof(double) * nB * K * 2);
+  st.out(&d_se, side_evaluated_out, sizeof(int32_t) * nB * K * 2);
+  st.out(&d_wk, segments_walked_out, sizeof(int32_t) * nB);
+  st.out(&d_stat, status, sizeof(int32_t) * nB);
+  if (int rc = st.upload()) return rc;
   MTG_HIP_TRY(ctx, time_begin(ctx));
   MTG_HIP_TRY(ctx, mtg::launch_collision_time_gradient(N, d_vals, d_times, *grid, d_grid, *params, increment_time, d_grad,
                                                        d_sc, d_se, d_wk, d_stat, batch, K, ctx->stream));
   MTG_HIP_TRY(ctx, time_end(ctx));
-  if (!dev) {
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(grad_t_out, base + o_grad, b_grad, hipMemcpyDeviceToHost, ctx->stream));
-    if (b_sc) MTG_HIP_TRY(ctx, hipMemcpyAsync(side_cost_out, base + o_sc, b_sc, hipMemcpyDeviceToHost, ctx->stream));
-    if (b_se) MTG_HIP_TRY(ctx, hipMemcpyAsync(side_evaluated_out, base + o_se, b_se, hipMemcpyDeviceToHost, ctx->stream));
-    if (b_wk) MTG_HIP_TRY(ctx, hipMemcpyAsync(segments_walked_out, base + o_wk, b_wk, hipMemcpyDeviceToHost, ctx->stream));
-    if (b_stat) MTG_HIP_TRY(ctx, hipMemcpyAsync(status, base + o_stat, b_stat, hipMemcpyDeviceToHost, ctx->stream));
-    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  } else if (!(flags & MTG_FLAG_ASYNC)) {
-    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return MTG_OK;
+  return st.finish();
 }
 
 int mtg_soft_constraint_cost_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* vertex_values,
@@ -1103,12 +1120,8 @@ int mtg_soft_constraint_cost_batch(mtg_ctx* ctx, int N, int D, int K, int64_t ba
   if (N < 6 || N > 12 || (N % 2)) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "N must be 6, 8, 10 or 12");
   if (D < 1 || D > 4) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "the soft-constraint term needs 1 <= D <= 4");
   if (K < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need K >= 1, batch >= 0");
-  if (!params || params->n_constraints < 1 || params->n_constraints > 8)
-    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "params with 1 <= n_constraints <= 8 are required");
-  const int C = params->n_constraints, kmax = N - 2 < 4 ? N - 2 : 4;
-  for (int c = 0; c < C; ++c)
-    if (params->derivative[c] < 0 || params->derivative[c] > kmax || !(params->limit[c] > 0.0))
-      return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "need 0 <= derivative <= min(4, N - 2) and limit > 0");
+  if (int rc = check_soft_params(ctx, N, params, "params with 1 <= n_constraints <= 8 are required")) return rc;
+  const int C = params->n_constraints;
   if (batch == 0) return MTG_OK;
   if (!vertex_values || !times || !cost_out || (grad_out && !fixed_mask))
     return set_error(ctx, MTG_ERR_INVALID_ARGUMENT,
@@ -1118,55 +1131,26 @@ int mtg_soft_constraint_cost_batch(mtg_ctx* ctx, int N, int D, int K, int64_t ba
   std::lock_guard<std::mutex> g(ctx->mu);
   MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int V = K + 1, h = N / 2;
-  const size_t b_vals = sizeof(double) * (size_t)batch * V * h * D, b_mask = grad_out ? (size_t)batch * V : 0,
-               b_times = sizeof(double) * (size_t)batch * K, b_cost = sizeof(double) * (size_t)batch,
-               b_grad = grad_out ? sizeof(double) * (size_t)batch * D * V * h : 0,
-               b_max = maxima_out ? sizeof(mtg_extremum) * (size_t)batch * C : 0,
-               b_stat = status ? sizeof(int32_t) * (size_t)batch : 0;
-  const double *d_vals = vertex_values, *d_times = times;
-  const uint8_t* d_mask = fixed_mask;
-  double *d_cost = cost_out, *d_grad = grad_out;
-  mtg_extremum* d_max = maxima_out;
-  int32_t* d_stat = status;
-  const bool dev = flags & MTG_FLAG_DEVICE_PTRS;
-  char* base = nullptr;
-  size_t o_cost = 0, o_grad = 0, o_max = 0, o_stat = 0;
-  if (!dev) {
-    size_t off = 0;
-    const size_t o_vals = off; off = align_up(off + b_vals);
-    const size_t o_mask = off; off = align_up(off + b_mask);
-    const size_t o_times = off; off = align_up(off + b_times);
-    o_cost = off; off = align_up(off + b_cost);
-    o_grad = off; off = align_up(off + b_grad);
-    o_max = off; off = align_up(off + b_max);
-    o_stat = off; off = align_up(off + b_stat);
-    MTG_HIP_TRY(ctx, ensure(&ctx->staging, &ctx->staging_bytes, std::max<size_t>(off, 256)));
-    base = static_cast<char*>(ctx->staging);
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_vals, vertex_values, b_vals, hipMemcpyHostToDevice, ctx->stream));
-    if (b_mask) MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_mask, fixed_mask, b_mask, hipMemcpyHostToDevice, ctx->stream));
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_times, times, b_times, hipMemcpyHostToDevice, ctx->stream));
-    d_vals = reinterpret_cast<const double*>(base + o_vals);
-    d_mask = b_mask ? reinterpret_cast<const uint8_t*>(base + o_mask) : nullptr;
-    d_times = reinterpret_cast<const double*>(base + o_times);
-    d_cost = reinterpret_cast<double*>(base + o_cost);
-    d_grad = grad_out ? reinterpret_cast<double*>(base + o_grad) : nullptr;
-    d_max = maxima_out ? reinterpret_cast<mtg_extremum*>(base + o_max) : nullptr;
-    d_stat = status ? reinterpret_cast<int32_t*>(base + o_stat) : nullptr;
-  }
+  const size_t nB = (size_t)batch;
+  const double *d_vals, *d_times;
+  const uint8_t* d_mask;
+  double *d_cost, *d_grad;
+  mtg_extremum* d_max;
+  int32_t* d_stat;
+  Staged st(ctx, flags);
+  st.in(&d_vals, vertex_values, sizeof(double) * nB * V * h * D);
+  st.in(&d_mask, fixed_mask, grad_out ? nB * V : 0);
+  st.in(&d_times, times, sizeof(double) * nB * K);
+  st.out(&d_cost, cost_out, sizeof(double) * nB);
+  st.out(&d_grad, grad_out, sizeof(double) * nB * D * V * h);
+  st.out(&d_max, maxima_out, sizeof(mtg_extremum) * nB * C);
+  st.out(&d_stat, status, sizeof(int32_t) * nB);
+  if (int rc = st.upload()) return rc;
   MTG_HIP_TRY(ctx, time_begin(ctx));  // (the kernel writes every entry of grad_out itself)
   MTG_HIP_TRY(ctx, mtg::launch_soft_constraint_cost(N, d_vals, d_mask, d_times, *params, d_cost, d_grad, d_max, d_stat,
                                                     batch, K, D, ctx->stream));
   MTG_HIP_TRY(ctx, time_end(ctx));
-  if (!dev) {
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(cost_out, base + o_cost, b_cost, hipMemcpyDeviceToHost, ctx->stream));
-    if (grad_out) MTG_HIP_TRY(ctx, hipMemcpyAsync(grad_out, base + o_grad, b_grad, hipMemcpyDeviceToHost, ctx->stream));
-    if (b_max) MTG_HIP_TRY(ctx, hipMemcpyAsync(maxima_out, base + o_max, b_max, hipMemcpyDeviceToHost, ctx->stream));
-    if (b_stat) MTG_HIP_TRY(ctx, hipMemcpyAsync(status, base + o_stat, b_stat, hipMemcpyDeviceToHost, ctx->stream));
-    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  } else if (!(flags & MTG_FLAG_ASYNC)) {
-    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return MTG_OK;
+  return st.finish();
 }
 
 int mtg_time_jacobian_batch(mtg_ctx* ctx, int N, int D, int K, int derivative_to_optimize,
@@ -1186,44 +1170,21 @@ int mtg_time_jacobian_batch(mtg_ctx* ctx, int N, int D, int K, int derivative_to
   std::lock_guard<std::mutex> g(ctx->mu);
   MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int V = K + 1, h = N / 2, C = n_candidates;
-  const size_t b_vals = sizeof(double) * (size_t)batch * V * h * D, b_times = sizeof(double) * (size_t)batch * K,
-               b_scales = sizeof(double) * (size_t)C * K, b_cost = sizeof(double) * (size_t)batch * C,
-               b_jac = jac_out ? sizeof(double) * (size_t)batch * C * K : 0;
-  const double *d_vals = vertex_values, *d_times = times, *d_scales = scales;
-  double *d_cost = cost_out, *d_jac = jac_out;
-  const bool dev = flags & MTG_FLAG_DEVICE_PTRS;
-  char* base = nullptr;
-  size_t o_cost = 0, o_jac = 0;
-  if (!dev) {
-    size_t off = 0;
-    const size_t o_vals = off; off = align_up(off + b_vals);
-    const size_t o_times = off; off = align_up(off + b_times);
-    const size_t o_scales = off; off = align_up(off + b_scales);
-    o_cost = off; off = align_up(off + b_cost);
-    o_jac = off; off = align_up(off + b_jac);
-    MTG_HIP_TRY(ctx, ensure(&ctx->staging, &ctx->staging_bytes, std::max<size_t>(off, 256)));
-    base = static_cast<char*>(ctx->staging);
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_vals, vertex_values, b_vals, hipMemcpyHostToDevice, ctx->stream));
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_times, times, b_times, hipMemcpyHostToDevice, ctx->stream));
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_scales, scales, b_scales, hipMemcpyHostToDevice, ctx->stream));
-    d_vals = reinterpret_cast<const double*>(base + o_vals);
-    d_times = reinterpret_cast<const double*>(base + o_times);
-    d_scales = reinterpret_cast<const double*>(base + o_scales);
-    d_cost = reinterpret_cast<double*>(base + o_cost);
-    d_jac = jac_out ? reinterpret_cast<double*>(base + o_jac) : nullptr;
-  }
+  const size_t nB = (size_t)batch;
+  const double *d_vals, *d_times, *d_scales;
+  double *d_cost, *d_jac;
+  Staged st(ctx, flags);
+  st.in(&d_vals, vertex_values, sizeof(double) * nB * V * h * D);
+  st.in(&d_times, times, sizeof(double) * nB * K);
+  st.in(&d_scales, scales, sizeof(double) * (size_t)C * K);
+  st.out(&d_cost, cost_out, sizeof(double) * nB * C);
+  st.out(&d_jac, jac_out, sizeof(double) * nB * C * K);
+  if (int rc = st.upload()) return rc;
   MTG_HIP_TRY(ctx, time_begin(ctx));
   MTG_HIP_TRY(ctx, mtg::launch_time_jacobian(N, derivative_to_optimize, d_vals, d_times, d_scales, d_cost, d_jac,
                                              increment_time, batch, K, D, C, ctx->stream));
   MTG_HIP_TRY(ctx, time_end(ctx));
-  if (!dev) {
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(cost_out, base + o_cost, b_cost, hipMemcpyDeviceToHost, ctx->stream));
-    if (jac_out) MTG_HIP_TRY(ctx, hipMemcpyAsync(jac_out, base + o_jac, b_jac, hipMemcpyDeviceToHost, ctx->stream));
-    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  } else if (!(flags & MTG_FLAG_ASYNC)) {
-    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return MTG_OK;
+  return st.finish();
 }
 
 // The objective in the optimiser's variables.  Launch sequence on the context's stream, no host
@@ -1251,13 +1212,8 @@ int mtg_objective_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const 
   int rc = check_shape(ctx, N, D, K, r, batch);
   if (rc != MTG_OK) return rc;
   if (with_coll) {
-    if (N < 6) return set_error(ctx, MTG_ERR_UNSUPPORTED_N, "N must be 6, 8, 10 or 12");
-    if (D != 3) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "the collision term needs D == 3");
-    if (!grid || !collision) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "grid and collision params are required");
-    if (!(collision->coll_check_time_increment > 0.0) || !(collision->map_resolution >= 0.0) ||
-        !(grid->resolution > 0.0) || grid->nx < 1 || grid->ny < 1 || grid->nz < 1)
-      return set_error(ctx, MTG_ERR_INVALID_ARGUMENT,
-                       "need coll_check_time_increment > 0, map_resolution >= 0, grid resolution > 0, grid dimensions >= 1");
+    rc = check_collision(ctx, N, D, K, batch, grid, collision, "grid and collision params are required");
+    if (rc != MTG_OK) return rc;
     if (with_time && !(params->increment_time > 0.0 && params->increment_time <= DBL_MAX))
       return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "increment_time must be > 0 and finite");
   } else if (D > 4) {
@@ -1268,13 +1224,9 @@ int mtg_objective_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const 
   int C = 0;
   if (with_soft) {
     if (N < 6 || D > 4) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "the soft-constraint term needs N >= 6, D <= 4");
-    if (soft->n_constraints < 1 || soft->n_constraints > 8)
-      return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "need 1 <= n_constraints <= 8");
+    rc = check_soft_params(ctx, N, soft, "need 1 <= n_constraints <= 8");
+    if (rc != MTG_OK) return rc;
     C = soft->n_constraints;
-    const int kmax = N - 2 < 4 ? N - 2 : 4;
-    for (int c = 0; c < C; ++c)
-      if (soft->derivative[c] < 0 || soft->derivative[c] > kmax || !(soft->limit[c] > 0.0))
-        return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "need 0 <= derivative <= min(4, N - 2) and limit > 0");
   }
   if (x_stride < 0) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "x_stride must be >= 0");
   if (batch == 0) return MTG_OK;
@@ -1322,52 +1274,28 @@ int mtg_objective_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const 
 
   // ---- staging of a host-pointer call: inputs and the objective's own outputs (the parts are copied
   // out of the workspace)
-  const size_t b_x = sizeof(double) * nB * (size_t)x_stride, b_mask = nB * V, b_state = state ? sizeof(mtg_objective_state) * nB : 0,
-               b_grid = with_coll ? sizeof(float) * (size_t)grid->nx * grid->ny * grid->nz : 0,
-               b_grad = with_grad ? b_x : 0, b_w = weighted_costs_out ? 4 * b_s : 0, b_co = collision_out ? nB : 0,
-               b_stat = status ? b_i : 0;
-  const double *d_x = x, *d_vals = values, *d_times = times;
-  const uint8_t* d_mask = fixed_mask;
-  const float* d_grid = with_coll ? grid->distance : nullptr;
-  double *d_cost = cost_out, *d_grad = grad_out, *d_w = weighted_costs_out;
-  uint8_t* d_co = collision_out;
-  mtg_objective_state* d_state = state;
-  int32_t* d_stat = status;
-  char* base = nullptr;
-  size_t o_cost = 0, o_grad = 0, o_w = 0, o_co = 0, o_state = 0, o_stat = 0;
-  if (!dev) {
-    size_t off = 0;
-    const size_t o_x = off; off = align_up(off + b_x);
-    const size_t o_vals = off; off = align_up(off + b_vv);
-    const size_t o_mask = off; off = align_up(off + b_mask);
-    const size_t o_times = off; off = align_up(off + (with_time ? 0 : b_T));
-    const size_t o_grid = off; off = align_up(off + b_grid);
-    o_state = off; off = align_up(off + b_state);
-    o_cost = off; off = align_up(off + b_s);
-    o_grad = off; off = align_up(off + b_grad);
-    o_w = off; off = align_up(off + b_w);
-    o_co = off; off = align_up(off + b_co);
-    o_stat = off; off = align_up(off + b_stat);
-    MTG_HIP_TRY(ctx, ensure(&ctx->staging, &ctx->staging_bytes, std::max<size_t>(off, 256)));
-    base = static_cast<char*>(ctx->staging);
-    if (b_x) MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_x, x, b_x, hipMemcpyHostToDevice, ctx->stream));
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_vals, values, b_vv, hipMemcpyHostToDevice, ctx->stream));
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_mask, fixed_mask, b_mask, hipMemcpyHostToDevice, ctx->stream));
-    if (!with_time) MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_times, times, b_T, hipMemcpyHostToDevice, ctx->stream));
-    if (b_grid) MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_grid, grid->distance, b_grid, hipMemcpyHostToDevice, ctx->stream));
-    if (b_state) MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_state, state, b_state, hipMemcpyHostToDevice, ctx->stream));
-    d_x = reinterpret_cast<const double*>(base + o_x);
-    d_vals = reinterpret_cast<const double*>(base + o_vals);
-    d_mask = reinterpret_cast<const uint8_t*>(base + o_mask);
-    d_times = with_time ? nullptr : reinterpret_cast<const double*>(base + o_times);
-    d_grid = b_grid ? reinterpret_cast<const float*>(base + o_grid) : nullptr;
-    d_state = b_state ? reinterpret_cast<mtg_objective_state*>(base + o_state) : nullptr;
-    d_cost = reinterpret_cast<double*>(base + o_cost);
-    d_grad = with_grad ? reinterpret_cast<double*>(base + o_grad) : nullptr;
-    d_w = b_w ? reinterpret_cast<double*>(base + o_w) : nullptr;
-    d_co = b_co ? reinterpret_cast<uint8_t*>(base + o_co) : nullptr;
-    d_stat = b_stat ? reinterpret_cast<int32_t*>(base + o_stat) : nullptr;
-  }
+  const size_t b_x = sizeof(double) * nB * (size_t)x_stride;
+  const double *d_x, *d_vals, *d_times;
+  const uint8_t* d_mask;
+  const float* d_grid;
+  double *d_cost, *d_grad, *d_w;
+  uint8_t* d_co;
+  mtg_objective_state* d_state;
+  int32_t* d_stat;
+  Staged st(ctx, flags);
+  st.in(&d_x, x, b_x);
+  st.in(&d_vals, values, b_vv);
+  st.in(&d_mask, fixed_mask, nB * V);
+  st.in(&d_times, times, with_time ? 0 : b_T);
+  st.in(&d_grid, with_coll ? grid->distance : nullptr, with_coll ? grid_bytes(*grid) : 0);
+  st.out(&d_cost, cost_out, b_s);
+  st.out(&d_grad, grad_out, b_x);
+  st.out(&d_w, weighted_costs_out, 4 * b_s);
+  st.out(&d_co, collision_out, nB);
+  st.inout(&d_state, state, sizeof(mtg_objective_state) * nB);
+  st.out(&d_stat, status, b_i);
+  rc = st.upload();
+  if (rc != MTG_OK) return rc;
 
   // ---- the launches
   MTG_HIP_TRY(ctx, time_begin(ctx, false));
@@ -1438,18 +1366,7 @@ int mtg_objective_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const 
       if (q.dst && q.have && q.bytes)
         MTG_HIP_TRY(ctx, hipMemcpyAsync(q.dst, ws + q.off, q.bytes, out_kind, ctx->stream));
   }
-  if (!dev) {
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(cost_out, base + o_cost, b_s, hipMemcpyDeviceToHost, ctx->stream));
-    if (b_grad) MTG_HIP_TRY(ctx, hipMemcpyAsync(grad_out, base + o_grad, b_grad, hipMemcpyDeviceToHost, ctx->stream));
-    if (b_w) MTG_HIP_TRY(ctx, hipMemcpyAsync(weighted_costs_out, base + o_w, b_w, hipMemcpyDeviceToHost, ctx->stream));
-    if (b_co) MTG_HIP_TRY(ctx, hipMemcpyAsync(collision_out, base + o_co, b_co, hipMemcpyDeviceToHost, ctx->stream));
-    if (b_state) MTG_HIP_TRY(ctx, hipMemcpyAsync(state, base + o_state, b_state, hipMemcpyDeviceToHost, ctx->stream));
-    if (b_stat) MTG_HIP_TRY(ctx, hipMemcpyAsync(status, base + o_stat, b_stat, hipMemcpyDeviceToHost, ctx->stream));
-    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  } else if (!(flags & MTG_FLAG_ASYNC)) {
-    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return MTG_OK;
+  return st.finish();
 }
 
 namespace {
@@ -1458,8 +1375,8 @@ namespace {
 int run_vertex_map(mtg_ctx* ctx, bool to_coeffs, int N, int D, int K, int64_t batch, const double* in,
                    const double* times, double* out, unsigned flags) {
   if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
-  if (N < 2 || N > 12 || (N % 2)) return set_error(ctx, MTG_ERR_UNSUPPORTED_N, "N must be even and in [2, 12]");
-  if (K < 1 || D < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need K >= 1, D >= 1, batch >= 0");
+  if (int rc = check_order(ctx, N)) return rc;
+  if (int rc = check_dims(ctx, D, K, batch)) return rc;
   if (!mtg::vertex_map_fits(N, D, K))
     return set_error(ctx, MTG_ERR_TOO_LARGE, "per-trajectory arrays exceed the LDS staging (reduce K or D)");
   if (batch == 0) return MTG_OK;
@@ -1467,37 +1384,18 @@ int run_vertex_map(mtg_ctx* ctx, bool to_coeffs, int N, int D, int K, int64_t ba
   std::lock_guard<std::mutex> g(ctx->mu);
   MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int V = K + 1, h = N / 2;
-  const size_t b_vals = sizeof(double) * (size_t)batch * V * h * D, b_coef = sizeof(double) * (size_t)batch * K * D * N,
-               b_times = sizeof(double) * (size_t)batch * K;
-  const size_t b_in = to_coeffs ? b_vals : b_coef, b_out = to_coeffs ? b_coef : b_vals;
-  const double *d_in = in, *d_times = times;
-  double* d_out = out;
-  const bool dev = flags & MTG_FLAG_DEVICE_PTRS;
-  char* base = nullptr;
-  size_t o_out = 0;
-  if (!dev) {
-    size_t off = 0;
-    const size_t o_in = off; off = align_up(off + b_in);
-    const size_t o_times = off; off = align_up(off + b_times);
-    o_out = off; off = align_up(off + b_out);
-    MTG_HIP_TRY(ctx, ensure(&ctx->staging, &ctx->staging_bytes, std::max<size_t>(off, 256)));
-    base = static_cast<char*>(ctx->staging);
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_in, in, b_in, hipMemcpyHostToDevice, ctx->stream));
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_times, times, b_times, hipMemcpyHostToDevice, ctx->stream));
-    d_in = reinterpret_cast<const double*>(base + o_in);
-    d_times = reinterpret_cast<const double*>(base + o_times);
-    d_out = reinterpret_cast<double*>(base + o_out);
-  }
+  const size_t nB = (size_t)batch, b_vals = sizeof(double) * nB * V * h * D, b_coef = sizeof(double) * nB * K * D * N;
+  const double *d_in, *d_times;
+  double* d_out;
+  Staged st(ctx, flags);
+  st.in(&d_in, in, to_coeffs ? b_vals : b_coef);
+  st.in(&d_times, times, sizeof(double) * nB * K);
+  st.out(&d_out, out, to_coeffs ? b_coef : b_vals);
+  if (int rc = st.upload()) return rc;
   MTG_HIP_TRY(ctx, time_begin(ctx));
   MTG_HIP_TRY(ctx, mtg::launch_vertex_map(to_coeffs, N, d_in, d_times, d_out, batch, K, D, ctx->stream));
   MTG_HIP_TRY(ctx, time_end(ctx));
-  if (!dev) {
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(out, base + o_out, b_out, hipMemcpyDeviceToHost, ctx->stream));
-    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  } else if (!(flags & MTG_FLAG_ASYNC)) {
-    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return MTG_OK;
+  return st.finish();
 }
 
 }  // namespace
@@ -1517,8 +1415,8 @@ int mtg_min_max_magnitude_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch
                                 const double* times, int derivative, uint32_t dimension_mask,
                                 mtg_extremum* minimum, mtg_extremum* maximum, unsigned flags) {
   if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
-  if (N < 2 || N > 12 || (N % 2)) return set_error(ctx, MTG_ERR_UNSUPPORTED_N, "N must be even and in [2, 12]");
-  if (K < 1 || D < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need K >= 1, D >= 1, batch >= 0");
+  if (int rc = check_order(ctx, N)) return rc;
+  if (int rc = check_dims(ctx, D, K, batch)) return rc;
   if (K > 256) return set_error(ctx, MTG_ERR_TOO_LARGE, "K must be <= 256");
   if (derivative < 0 || derivative > N - 2)
     return set_error(ctx, MTG_ERR_BAD_DERIVATIVE, "derivative must be in [0, N-2] (polynomial.cpp:62-65)");
@@ -1529,40 +1427,20 @@ int mtg_min_max_magnitude_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch
   if (!coeffs || !times) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "coeffs and times are required");
   std::lock_guard<std::mutex> g(ctx->mu);
   MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t b_coef = sizeof(double) * (size_t)batch * K * D * N, b_times = sizeof(double) * (size_t)batch * K,
-               b_ext = sizeof(mtg_extremum) * (size_t)batch;
-  const double *d_coef = coeffs, *d_times = times;
-  mtg_extremum *d_min = minimum, *d_max = maximum;
-  const bool dev = flags & MTG_FLAG_DEVICE_PTRS;
-  char* base = nullptr;
-  size_t o_min = 0, o_max = 0;
-  if (!dev) {
-    size_t off = 0;
-    const size_t o_coef = off; off = align_up(off + b_coef);
-    const size_t o_times = off; off = align_up(off + b_times);
-    o_min = off; off = align_up(off + b_ext);
-    o_max = off; off = align_up(off + b_ext);
-    MTG_HIP_TRY(ctx, ensure(&ctx->staging, &ctx->staging_bytes, std::max<size_t>(off, 256)));
-    base = static_cast<char*>(ctx->staging);
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_coef, coeffs, b_coef, hipMemcpyHostToDevice, ctx->stream));
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_times, times, b_times, hipMemcpyHostToDevice, ctx->stream));
-    d_coef = reinterpret_cast<const double*>(base + o_coef);
-    d_times = reinterpret_cast<const double*>(base + o_times);
-    d_min = minimum ? reinterpret_cast<mtg_extremum*>(base + o_min) : nullptr;
-    d_max = maximum ? reinterpret_cast<mtg_extremum*>(base + o_max) : nullptr;
-  }
+  const size_t nB = (size_t)batch;
+  const double *d_coef, *d_times;
+  mtg_extremum *d_min, *d_max;
+  Staged st(ctx, flags);
+  st.in(&d_coef, coeffs, sizeof(double) * nB * K * D * N);
+  st.in(&d_times, times, sizeof(double) * nB * K);
+  st.out(&d_min, minimum, sizeof(mtg_extremum) * nB);
+  st.out(&d_max, maximum, sizeof(mtg_extremum) * nB);
+  if (int rc = st.upload()) return rc;
   MTG_HIP_TRY(ctx, time_begin(ctx));
   MTG_HIP_TRY(ctx, mtg::launch_min_max_magnitude(N, d_coef, d_times, batch, K, D, derivative, dims, d_min, d_max,
                                                  ctx->stream));
   MTG_HIP_TRY(ctx, time_end(ctx));
-  if (!dev) {
-    if (minimum) MTG_HIP_TRY(ctx, hipMemcpyAsync(minimum, base + o_min, b_ext, hipMemcpyDeviceToHost, ctx->stream));
-    if (maximum) MTG_HIP_TRY(ctx, hipMemcpyAsync(maximum, base + o_max, b_ext, hipMemcpyDeviceToHost, ctx->stream));
-    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  } else if (!(flags & MTG_FLAG_ASYNC)) {
-    MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return MTG_OK;
+  return st.finish();
 }
 
 int mtg_evaluate_range_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch,
@@ -1571,8 +1449,8 @@ int mtg_evaluate_range_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch,
                              const int64_t* offsets, double* out, double* sample_times,
                              unsigned flags) {
   if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
-  if (N < 2 || N > 12 || (N % 2)) return set_error(ctx, MTG_ERR_UNSUPPORTED_N, "N must be even and in [2, 12]");
-  if (K < 1 || D < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need K >= 1, D >= 1, batch >= 0");
+  if (int rc = check_order(ctx, N)) return rc;
+  if (int rc = check_dims(ctx, D, K, batch)) return rc;
   if (!(dt > 0.0) || derivative < 0)
     return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "dt must be > 0 and derivative >= 0");
   if (batch == 0) return MTG_OK;
@@ -1649,7 +1527,7 @@ int mtg_evaluate_range_batch_full(mtg_ctx* ctx, int N, int D, int K, int64_t bat
                                   int64_t* counts, int64_t* offsets, int64_t* total, double* out,
                                   double* sample_times, int64_t capacity, unsigned flags) {
   if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
-  if (N < 2 || N > 12 || (N % 2)) return set_error(ctx, MTG_ERR_UNSUPPORTED_N, "N must be even and in [2, 12]");
+  if (int rc = check_order(ctx, N)) return rc;
   if (K < 1 || D < 1 || batch < 0 || capacity < 0)
     return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need K >= 1, D >= 1, batch >= 0, capacity >= 0");
   if (!(dt > 0.0) || derivative < 0)

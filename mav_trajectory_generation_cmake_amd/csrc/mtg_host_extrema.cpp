@@ -49,29 +49,10 @@ extern "C" int mtg_host_min_max_magnitude_batch(int N, int D, int K, int64_t bat
   if (batch == 0) return MTG_OK;
   if (!coeffs || !times) return MTG_ERR_INVALID_ARGUMENT;
   const size_t sc = (size_t)K * D * N;
-  auto run = [&](int64_t b0, int64_t b1) {
+  mtg::run_threads(batch, threads, [&](int64_t b0, int64_t b1) {
     for (int64_t b = b0; b < b1; ++b)
       one(N, D, K, coeffs + b * sc, times + b * K, derivative, dims, minimum ? minimum + b : nullptr,
           maximum ? maximum + b : nullptr);
-  };
-  int nt = threads > 0 ? threads : mtg::usable_cpus();
-  if (nt < 1) nt = 1;
-  if ((int64_t)nt > batch) nt = (int)batch;
-  if (nt == 1) {
-    run(0, batch);
-    return MTG_OK;
-  }
-  std::vector<std::thread> pool;
-  const int64_t per = (batch + nt - 1) / nt;
-  for (int t = 1; t < nt; ++t) {
-    const int64_t b0 = std::min<int64_t>(batch, t * per), b1 = std::min<int64_t>(batch, b0 + per);
-    try {
-      pool.emplace_back(run, b0, b1);
-    } catch (...) {
-      run(b0, b1);
-    }
-  }
-  run(0, std::min<int64_t>(batch, per));
-  for (auto& th : pool) th.join();
+  });
   return MTG_OK;
 }

@@ -96,29 +96,6 @@ void derivative_term(int N, int D, int K, int r, const double* vv, const uint8_t
   }
 }
 
-template <typename F>
-void run_threads(int64_t batch, int threads, F run) {
-  int nt = threads > 0 ? threads : mtg::usable_cpus();
-  if (nt < 1) nt = 1;
-  if ((int64_t)nt > batch) nt = (int)batch;
-  if (nt <= 1) {
-    run(0, batch);
-    return;
-  }
-  std::vector<std::thread> pool;
-  const int64_t per = (batch + nt - 1) / nt;
-  for (int t = 1; t < nt; ++t) {
-    const int64_t b0 = std::min<int64_t>(batch, t * per), b1 = std::min<int64_t>(batch, b0 + per);
-    try {
-      pool.emplace_back(run, b0, b1);
-    } catch (...) {
-      run(b0, b1);
-    }
-  }
-  run(0, std::min<int64_t>(batch, per));
-  for (auto& th : pool) th.join();
-}
-
 }  // namespace
 
 extern "C" int mtg_host_objective_batch(int N, int D, int K, int64_t batch, const double* values,
@@ -196,7 +173,7 @@ extern "C" int mtg_host_objective_batch(int N, int D, int K, int64_t batch, cons
     rc = mtg_host_collision_time_gradient_batch(N, D, K, batch, vv.data(), T.data(), grid, collision,
                                                 params->increment_time, jc.data(), nullptr, nullptr, st_t.data(), threads);
   if (rc != MTG_OK) return rc;
-  run_threads(batch, threads, [&](int64_t b0, int64_t b1) {
+  mtg::run_threads(batch, threads, [&](int64_t b0, int64_t b1) {
     Work w;
     for (int64_t b = b0; b < b1; ++b) {
       if (st[b] & MTG_TRAJ_BAD_TIME) {

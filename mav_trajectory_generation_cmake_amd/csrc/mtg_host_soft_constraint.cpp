@@ -117,31 +117,12 @@ extern "C" int mtg_host_soft_constraint_cost_batch(int N, int D, int K, int64_t 
   if (batch == 0) return MTG_OK;
   if (!vertex_values || !times || !cost_out || (grad_out && !fixed_mask)) return MTG_ERR_INVALID_ARGUMENT;
   const int h = N / 2, V = K + 1, C = params->n_constraints;
-  auto run = [&](int64_t b0, int64_t b1) {
+  mtg::run_threads(batch, threads, [&](int64_t b0, int64_t b1) {
     Work w;
     for (int64_t b = b0; b < b1; ++b)
       one(N, D, K, vertex_values + b * (int64_t)V * h * D, fixed_mask ? fixed_mask + b * V : nullptr, times + b * K,
           *params, cost_out + b, grad_out ? grad_out + b * (int64_t)D * V * h : nullptr,
           maxima_out ? maxima_out + b * C : nullptr, status ? status + b : nullptr, w);
-  };
-  int nt = threads > 0 ? threads : mtg::usable_cpus();
-  if (nt < 1) nt = 1;
-  if ((int64_t)nt > batch) nt = (int)batch;
-  if (nt == 1) {
-    run(0, batch);
-    return MTG_OK;
-  }
-  std::vector<std::thread> pool;
-  const int64_t per = (batch + nt - 1) / nt;
-  for (int t = 1; t < nt; ++t) {
-    const int64_t b0 = std::min<int64_t>(batch, t * per), b1 = std::min<int64_t>(batch, b0 + per);
-    try {
-      pool.emplace_back(run, b0, b1);
-    } catch (...) {
-      run(b0, b1);
-    }
-  }
-  run(0, std::min<int64_t>(batch, per));
-  for (auto& th : pool) th.join();
+  });
   return MTG_OK;
 }

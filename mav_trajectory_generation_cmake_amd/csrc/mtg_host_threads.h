@@ -8,10 +8,13 @@
 
 #include <sched.h>
 
+#include <algorithm>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <thread>
+#include <vector>
 
 namespace mtg {
 
@@ -115,6 +118,32 @@ inline int usable_cpus_uncached() {
 inline int usable_cpus() {
   static const int n = usable_cpus_uncached();
   return n;
+}
+
+// run(b0, b1) over [0, batch) in blocks of per = ceil(batch / nt), nt = threads (<= 0: usable_cpus())
+// capped by batch: thread t takes [t per, min(batch, (t + 1) per)), the caller's thread the first
+// block.  A block whose thread cannot be created runs on the caller's thread.
+template <typename F>
+void run_threads(int64_t batch, int threads, F run) {
+  int nt = threads > 0 ? threads : usable_cpus();
+  if (nt < 1) nt = 1;
+  if ((int64_t)nt > batch) nt = (int)batch;
+  if (nt <= 1) {
+    run(0, batch);
+    return;
+  }
+  std::vector<std::thread> pool;
+  const int64_t per = (batch + nt - 1) / nt;
+  for (int t = 1; t < nt; ++t) {
+    const int64_t b0 = std::min<int64_t>(batch, t * per), b1 = std::min<int64_t>(batch, b0 + per);
+    try {
+      pool.emplace_back(run, b0, b1);
+    } catch (...) {
+      run(b0, b1);
+    }
+  }
+  run(0, std::min<int64_t>(batch, per));
+  for (auto& th : pool) th.join();
 }
 
 }  // namespace mtg
