@@ -216,6 +216,25 @@ class BatchPolynomialOptimization {
                               cost, grad, weighted_costs, is_collision, state, parts, status, flags),
           ctx_, "mtg_objective_batch");
   }
+  // The two gradient-free objectives in the segment times, one cost per trajectory
+  // (mtg_objective_time_batch: objectiveFunctionTime, nl_impl:765-832, and
+  // objectiveFunctionTimeAndConstraints, :835-906).  x [B][x_stride]: the K times (objective 4: then D
+  // blocks of n_free[b] free derivatives); params.derivative_to_optimize is set to this object's.
+  // coeff_times / grid / collision iff objective 3 with w_c > 0; constraints NULL only with the soft
+  // constraints off and neither constraint_values nor maxima requested.
+  void objectiveTime(int64_t batch, const double* values, const uint8_t* mask, const double* x, int64_t x_stride,
+                     mtg_objective_time_params params, const double* coeff_times, const mtg_sdf_grid* grid,
+                     const mtg_collision_params* collision, const mtg_soft_constraint_params* constraints, double* cost,
+                     double* weighted_costs = nullptr, uint8_t* is_collision = nullptr,
+                     double* constraint_values = nullptr, mtg_extremum* maxima = nullptr, double* free = nullptr,
+                     double* coeffs = nullptr, mtg_objective_state* state = nullptr,
+                     const mtg_objective_parts* parts = nullptr, int32_t* status = nullptr, unsigned flags = 0) {
+    params.derivative_to_optimize = r_;
+    check(mtg_objective_time_batch(ctx_, N, D_, K_, batch, values, mask, x, x_stride, &params, coeff_times, grid,
+                                   collision, constraints, cost, weighted_costs, is_collision, constraint_values, maxima,
+                                   free, coeffs, state, parts, status, flags),
+          ctx_, "mtg_objective_time_batch");
+  }
   void coefficientsFromVertices(int64_t batch, const double* vertex_values, const double* times, double* coeffs,
                                 unsigned flags = 0) {
     check(mtg_coefficients_from_vertices_batch(ctx_, N, D_, K_, batch, vertex_values, times, coeffs, flags), ctx_,
@@ -336,6 +355,33 @@ inline void objective(int D, int K, int64_t batch, const double* values, const u
     check(mtg_host_objective_batch(N, D, K, batch, values, mask, times, x, x_stride, &params, grid, collision, soft, cost,
                                    grad, weighted_costs, is_collision, state, parts, status, 1),
           nullptr, "mtg_host_objective_batch");
+  }
+}
+
+// objectiveFunctionTime / objectiveFunctionTimeAndConstraints (mtg_objective_time_batch) for
+// trajectories of N coefficients, K segments and D dimensions, without a BatchPolynomialOptimization
+// object: on the library's host path (mtg_host_objective_time_batch) unless the execution policy is
+// kDevice, as objective.  Host pointers.
+template <int N>
+inline void objectiveTime(int D, int K, int64_t batch, const double* values, const uint8_t* mask, const double* x,
+                          int64_t x_stride, const mtg_objective_time_params& params, const double* coeff_times,
+                          const mtg_sdf_grid* grid, const mtg_collision_params* collision,
+                          const mtg_soft_constraint_params* constraints, double* cost, double* weighted_costs = nullptr,
+                          uint8_t* is_collision = nullptr, double* constraint_values = nullptr,
+                          mtg_extremum* maxima = nullptr, double* free = nullptr, double* coeffs = nullptr,
+                          mtg_objective_state* state = nullptr, const mtg_objective_parts* parts = nullptr,
+                          int32_t* status = nullptr) {
+  if (singleOnDevice()) {
+    mtg_ctx* ctx = defaultContext();
+    check(mtg_objective_time_batch(ctx, N, D, K, batch, values, mask, x, x_stride, &params, coeff_times, grid, collision,
+                                   constraints, cost, weighted_costs, is_collision, constraint_values, maxima, free,
+                                   coeffs, state, parts, status, 0),
+          ctx, "mtg_objective_time_batch");
+  } else {
+    check(mtg_host_objective_time_batch(N, D, K, batch, values, mask, x, x_stride, &params, coeff_times, grid, collision,
+                                        constraints, cost, weighted_costs, is_collision, constraint_values, maxima, free,
+                                        coeffs, state, parts, status, 1),
+          nullptr, "mtg_host_objective_time_batch");
   }
 }
 

@@ -46,9 +46,11 @@
 extern "C" {
 #endif
 
-#define MTG_ABI_VERSION 4   /* 2: + mtg_soft_constraint_cost_batch, mtg_host_soft_constraint_cost_batch
+#define MTG_ABI_VERSION 5   /* 2: + mtg_soft_constraint_cost_batch, mtg_host_soft_constraint_cost_batch
                                3: + mtg_collision_time_gradient_batch, mtg_host_collision_time_gradient_batch
-                               4: + mtg_objective_batch, mtg_host_objective_batch, mtg_host_objective_bounds_batch */
+                               4: + mtg_objective_batch, mtg_host_objective_batch, mtg_host_objective_bounds_batch
+                               5: + mtg_objective_time_batch, mtg_host_objective_time_batch,
+                                    mtg_host_objective_time_bounds_batch */
 
 /* Call-level return codes. */
 #define MTG_OK 0
@@ -67,7 +69,7 @@ extern "C" {
 #define MTG_TRAJ_NOT_SPD 2             /* non-positive pivot in R_pp (reference: undetected, lin_impl:355-368),
                                           or some 0 < T < DBL_EPSILON, where the reference's A(T) is
                                           singular (baseCoeffsWithTime, polynomial.h:225) */
-#define MTG_TRAJ_ROW_TOO_SHORT 4        /* mtg_objective_batch with MTG_FLAG_DEVICE_PTRS: x_stride is shorter than
+#define MTG_TRAJ_ROW_TOO_SHORT 4        /* mtg_objective[_time]_batch with MTG_FLAG_DEVICE_PTRS: x_stride is shorter than
                                           this trajectory's row (a host-pointer call returns
                                           MTG_ERR_INVALID_ARGUMENT instead); its x is not read */
 #define MTG_TRAJ_WARN_DROPPED 256      /* constraint of order > N/2-1 ignored (LOG(WARNING) lin_impl:84-87) */
@@ -110,8 +112,8 @@ extern "C" {
 #define MTG_KERNEL_GENERAL 3           /* general LDS-resident fused kernel (any K) */
 #define MTG_KERNEL_SPLIT 4             /* assembly kernel + block-Cholesky kernel */
 #define MTG_KERNEL_DL 6                /* one lane per (chain, dimension) (MTG_FLAG_DL_KERNEL) */
-#define MTG_KERNEL_DLX 7               /* the same for chains of other lengths (N = 10 / 12, D <= 4, r >= 1,
-                                          where neither the DL nor the column kernel applies: e.g. the
+#define MTG_KERNEL_DLX 7               /* the same for chains of other lengths (N = 6 / 8 / 10 / 12, D <= 4,
+                                          r >= 1, where neither the DL nor the column kernel applies: e.g. the
                                           reference benchmark's K = 50 / 100), plus the general kernel's
                                           block function for trajectories whose interior vertices do not
                                           fix exactly their position */
@@ -509,11 +511,12 @@ int mtg_host_soft_constraint_cost_batch(int N, int D, int K, int64_t batch, cons
 #define MTG_OBJECTIVE_FREE_CONSTRAINTS 0                        /* objectiveFunctionFreeConstraints, nl_impl:909-1000 */
 #define MTG_OBJECTIVE_FREE_CONSTRAINTS_AND_COLLISION 1          /* ...AndCollision, nl_impl:1003-1156 */
 #define MTG_OBJECTIVE_FREE_CONSTRAINTS_AND_COLLISION_AND_TIME 2 /* ...AndCollisionAndTime, nl_impl:1159-1449 */
-/* Not covered, MTG_ERR_INVALID_ARGUMENT: the two solve-based objectives (objectiveFunctionTime,
- * objectiveFunctionTimeAndConstraints) as values of `objective`, and the reference's numerical-gradient
- * switches as bits of mtg_objective_params.reserved (any non-zero `reserved` is rejected). */
-#define MTG_OBJECTIVE_TIME 3                                    /* not covered */
-#define MTG_OBJECTIVE_TIME_AND_CONSTRAINTS 4                    /* not covered */
+/* The two gradient-free objectives (objectiveFunctionTime, objectiveFunctionTimeAndConstraints) are
+ * values of mtg_objective_time_params.objective (mtg_objective_time_batch, below); mtg_objective_batch
+ * rejects them with MTG_ERR_INVALID_ARGUMENT.  Not covered anywhere: the reference's numerical-gradient
+ * switches, bits of mtg_objective_params.reserved (any non-zero `reserved` is rejected). */
+#define MTG_OBJECTIVE_TIME 3                                    /* objectiveFunctionTime, nl_impl:765-832 */
+#define MTG_OBJECTIVE_TIME_AND_CONSTRAINTS 4                    /* ...TimeAndConstraints, nl_impl:835-906 */
 #define MTG_OBJECTIVE_USE_NUMERIC_GRAD 1                        /* use_numeric_grad: not covered */
 #define MTG_OBJECTIVE_SIMPLE_NUMGRAD_TIME 2                     /* is_simple_numgrad_time: not covered */
 #define MTG_OBJECTIVE_SIMPLE_NUMGRAD_CONSTRAINTS 4              /* is_simple_numgrad_constraints: not covered */
@@ -648,6 +651,134 @@ int mtg_host_objective_bounds_batch(int N, int D, int K, int64_t batch, const ui
                                     const mtg_soft_constraint_params* constraints, const double* min_bound,
                                     const double* max_bound, double initial_stepsize_rel, double* lower,
                                     double* upper, double* initial_step);
+
+/* ---- The two gradient-free objectives in the segment times: objectiveFunctionTime (nl_impl:765-832,
+ * kOptimizeTime, reached through optimizeTime()) and objectiveFunctionTimeAndConstraints
+ * (nl_impl:835-906, kOptimizeFreeConstraintsAndTime: the default `objective` of
+ * NonlinearOptimizationParameters, polynomial_optimization_nonlinear.h:60).  The reference CHECKs
+ * gradient.empty() in both (:768, :838), so there is no gradient argument. */
+typedef struct mtg_objective_time_params {
+  int32_t objective;               /* MTG_OBJECTIVE_TIME or MTG_OBJECTIVE_TIME_AND_CONSTRAINTS; others: INVALID_ARGUMENT */
+  int32_t derivative_to_optimize;
+  double  time_penalty;            /* reference default 500 */
+  double  w_c;                     /* objective 3 only; the collision term exists iff w_c > 0 (nl_impl:789) */
+  int32_t use_soft_constraints;
+  int32_t reserved;                /* must be 0 */
+} mtg_objective_time_params;
+
+/* One evaluation of objectiveFunctionTime (objective 3) or objectiveFunctionTimeAndConstraints
+ * (objective 4) per trajectory.  values / fixed_mask are the problem as mtg_solve_linear_batch reads
+ * it; row b of x [B][x_stride] is the vector nlopt sees:
+ *   objective 3: the K segment times, and nothing else;
+ *   objective 4: the K times, then D blocks of n_free[b] free derivatives in the layout of
+ *                mtg_objective_batch objective 2.
+ * x_stride must be at least the longest row (else MTG_ERR_INVALID_ARGUMENT; with MTG_FLAG_DEVICE_PTRS
+ * the check is made per trajectory on the device and reported as MTG_TRAJ_ROW_TOO_SHORT, an error bit
+ * like the others); entries of x past a row's length are not read.
+ *
+ * Semantics.  Every product and every sum below rounds on its own and is evaluated left to right.
+ * T = the times from x.
+ * Objective 3 (nl_impl:765-832):
+ *   ct, the free derivatives and the coefficients = cost_out, free_out and coeffs of
+ *     mtg_solve_linear_batch(values, fixed_mask, T, flags = 0) (updateSegmentTimes + solveLinear +
+ *     computeCost, :779-782): the bytes of the default kernel for the shape, whichever it is.
+ *   J_t = T_0 + T_1 + ... (sequential, computeTotalTrajectoryTime); ctime = (J_t * J_t) * time_penalty (:784-785).
+ *   vertex_values = the fixed entries from `values`, the free ones from the solve (setFreeConstraints' layout).
+ *   cs = the cost of mtg_soft_constraint_cost_batch(vertex_values, T, constraints) when
+ *     use_soft_constraints is set, else 0 (:795-801).  cs is unweighted: the reference applies no w_sc here.
+ *   cc = w_c * J_c when w_c > 0, else 0 (:787-793).  J_c is the loop documented at
+ *     mtg_collision_cost_batch with its clock bounds and end-of-segment correction taken from T, and its
+ *     coefficients c_i = A(Tc_i)^-1 [x_i; x_{i+1}] with Tc = coeff_times[b] [B][K]: optimizeTime forms L_
+ *     once from the initial times (:259-264) and objectiveFunctionTime never refreshes it, while
+ *     getCostAndGradientCollision takes its coefficients as L_ * d (:1558) and its loop bounds from
+ *     getSegmentTimes (:1563) -- the stale L_ documented at mtg_collision_time_gradient_batch.
+ *     coeff_times is required when w_c > 0.  No semantics is invented for a refreshed L_: a caller who
+ *     wants one passes coeff_times equal to the times in x.
+ *   cost = ((ct + cc) + ctime) + cs (:831).  State (:817-829): n_iterations++, the four costs; if
+ *     !iter0_done: total_cost_iter0 = cost, iter0_done = 1.
+ * Objective 4 (nl_impl:835-906):
+ *   vertex_values = the fixed entries from `values`, the free ones from x (setFreeConstraints, :871).
+ *   ct = 0.5 * J_d with J_d from mtg_cost_at_times_batch (one candidate, scales of 1): the reference's
+ *     computeCost() after updateSegmentTimes + setFreeConstraints (:870-873).  The halving is exact, so
+ *     ct's bits are defined by that entry point.
+ *   ctime and cs as in objective 3 (:877-886).  There is no collision term: grid, collision and
+ *     coeff_times must be NULL, and w_c is not read.
+ *   cost = (ct + ctime) + cs (:905).  State (:899-903): n_iterations++, cost_trajectory, cost_time and
+ *     cost_soft_constraints; cost_collision, total_cost_iter0 and iter0_done are left as they were.
+ * state == NULL behaves as an all-zero state that is thrown away.
+ * Outputs of both objectives (cost_out [B] is required, every other output is nullable, and requesting
+ * one does not change the bits of cost_out or state):
+ *   weighted_costs_out [B][4] = ct, cc (or 0), ctime, cs.
+ *   collision_out [B]: the collision flag of J_c's walk (0 without a collision term).
+ *   maxima_out [B][n_constraints] = the maxima of mtg_soft_constraint_cost_batch;
+ *   constraint_values_out [B][n_constraints], entry c = maxima[c].value - limit[c]: what
+ *     evaluateMaximumMagnitudeConstraint returns to nlopt for a hard inequality constraint
+ *     (nl_impl:2346-2392).  Both are available whether or not use_soft_constraints is set: with it off and
+ *     either requested, the maxima search runs and its cost is discarded.  `constraints` may be NULL only
+ *     if use_soft_constraints is off and neither is requested.
+ *   free_out [B][D][V*h] (entries >= n_free are 0) and coeffs_out [B][K][D][N] describe the trajectory at
+ *     x: objective 3: the solve's own outputs; objective 4: the free part of x, and the coefficients of
+ *     mtg_coefficients_from_vertices_batch(vertex_values, T).
+ *   parts (nullable): J_d (objective 4 only), J_c, J_sc and J_t are filled as the components return
+ *     them; its gradient fields (dJd_dt, dJc_dt, grad_d, grad_c, grad_sc) must be NULL.
+ *
+ * Shapes and errors.  w_c > 0 (objective 3) requires D = 3, N in {6, 8, 10, 12} and non-NULL grid,
+ * collision and coeff_times; otherwise 1 <= D <= 4 and those three must be NULL.  The soft-constraint
+ * search needs N in {6, 8, 10, 12}.  K is limited by the smaller LDS limit of the components used
+ * (MTG_ERR_TOO_LARGE).  MTG_ERR_INVALID_ARGUMENT: an objective other than 3 or 4, reserved != 0, a
+ * missing or an extra grid / collision / coeff_times, a non-NULL gradient field of parts.
+ * status [B] (nullable) is the OR of the solve's bits (objective 3: MTG_TRAJ_BAD_TIME, MTG_TRAJ_NOT_SPD,
+ * MTG_TRAJ_WARN_DROPPED) and of the components' bits; a time in x or an entry of coeff_times that is
+ * not positive and finite gives MTG_TRAJ_BAD_TIME.  For a trajectory with an error bit every floating
+ * output of its row is NaN (maxima: time and value NaN, segment 0), collision_out is 0 and its state
+ * is left as it was: the rule of mtg_objective_batch.  The parts are exempt, as there.
+ *
+ * Device call: one stream, no host synchronisation between the kernels; intermediates live in the
+ * context-owned workspace.  Objective 3: times-unpack | solve | assemble | [soft
+ * constraints] | [collision with coefficient times] | combine; objective 4: unpack | cost | [soft
+ * constraints] | [coefficients] | combine.  MTG_FLAG_DEVICE_PTRS and MTG_FLAG_ASYNC as in
+ * mtg_objective_batch.  Results do not depend on the trajectory's place in the batch or on the batch. */
+int mtg_objective_time_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* values,
+                             const uint8_t* fixed_mask, const double* x, int64_t x_stride,
+                             const mtg_objective_time_params* params, const double* coeff_times,
+                             const mtg_sdf_grid* grid, const mtg_collision_params* collision,
+                             const mtg_soft_constraint_params* constraints, double* cost_out,
+                             double* weighted_costs_out, uint8_t* collision_out, double* constraint_values_out,
+                             mtg_extremum* maxima_out, double* free_out, double* coeffs_out,
+                             mtg_objective_state* state, const mtg_objective_parts* parts, int32_t* status,
+                             unsigned flags);
+
+/* Host (CPU) path of mtg_objective_time_batch, no context and no GPU needed: composed of
+ * mtg_host_solve_linear_batch (objective 3), mtg_host_soft_constraint_cost_batch, the host collision
+ * loop of mtg_host_collision_cost_batch with the coefficients formed at coeff_times, the host J_d of
+ * mtg_host_objective_batch (objective 4) and mtg_host_coefficients_from_vertices_batch; the
+ * combination is the same code as the device's.  All host pointers; threads <= 0:
+ * mtg_host_default_threads(). */
+int mtg_host_objective_time_batch(int N, int D, int K, int64_t batch, const double* values,
+                                  const uint8_t* fixed_mask, const double* x, int64_t x_stride,
+                                  const mtg_objective_time_params* params, const double* coeff_times,
+                                  const mtg_sdf_grid* grid, const mtg_collision_params* collision,
+                                  const mtg_soft_constraint_params* constraints, double* cost_out,
+                                  double* weighted_costs_out, uint8_t* collision_out, double* constraint_values_out,
+                                  mtg_extremum* maxima_out, double* free_out, double* coeffs_out,
+                                  mtg_objective_state* state, const mtg_objective_parts* parts, int32_t* status,
+                                  int threads);
+
+/* Bounds and initial step of the two set-ups (host only), restated literally.  x [B][x_stride] in the
+ * layout of mtg_objective_time_batch, `objective` as in mtg_objective_time_params.
+ *   MTG_OBJECTIVE_TIME (optimizeTime, nl_impl:248-256 and :273-276), for each of the K times t:
+ *     initial_step = initial_stepsize_rel * t, lower = 0.1, upper = t * 2.
+ *   MTG_OBJECTIVE_TIME_AND_CONSTRAINTS (optimizeTimeAndFreeConstraints, nl_impl:551-562), for every
+ *     entry of the row: initial_step = initial_stepsize_rel * |x|, lower = -|x| * 2, upper = |x| * 2;
+ *     then lower = 0.1 for the K times.
+ * fixed_mask [B][V] gives the rows' lengths (objective 4; not read for objective 3).  lower, upper,
+ * initial_step [B][x_stride] (each nullable); entries past a row's length are +0.0, as in
+ * mtg_host_objective_bounds_batch.  MTG_ERR_INVALID_ARGUMENT: another objective, x_stride shorter than
+ * a row. */
+int mtg_host_objective_time_bounds_batch(int N, int D, int K, int64_t batch, const uint8_t* fixed_mask,
+                                         int objective, const double* x, int64_t x_stride,
+                                         double initial_stepsize_rel, double* lower, double* upper,
+                                         double* initial_step);
 
 /* Timing of the most recent kernel launch(es) of this context on its stream
  * (hipEvent pair around the solve kernel), in milliseconds. */

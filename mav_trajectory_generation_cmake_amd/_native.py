@@ -48,8 +48,8 @@ KERNEL_NAMES = {MTG_KERNEL_COLUMN: "solve_reg_kernel",
 MTG_OBJECTIVE_FREE_CONSTRAINTS = 0
 MTG_OBJECTIVE_FREE_CONSTRAINTS_AND_COLLISION = 1
 MTG_OBJECTIVE_FREE_CONSTRAINTS_AND_COLLISION_AND_TIME = 2
-MTG_OBJECTIVE_TIME = 3                      # not covered
-MTG_OBJECTIVE_TIME_AND_CONSTRAINTS = 4      # not covered
+MTG_OBJECTIVE_TIME = 3                      # mtg_objective_time_batch (mtg_objective_batch rejects 3 and 4)
+MTG_OBJECTIVE_TIME_AND_CONSTRAINTS = 4
 MTG_OBJECTIVE_USE_NUMERIC_GRAD = 1          # bits of ObjectiveParams.reserved: not covered
 MTG_OBJECTIVE_SIMPLE_NUMGRAD_TIME = 2
 MTG_OBJECTIVE_SIMPLE_NUMGRAD_CONSTRAINTS = 4
@@ -85,6 +85,13 @@ class ObjectiveParams(ctypes.Structure):
                 ("increment_time", ctypes.c_double), ("use_soft_constraints", ctypes.c_int32),
                 ("is_collision_safe", ctypes.c_int32), ("is_coll_raise_first_iter", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("add_coll_raise", ctypes.c_double)]
+
+
+class ObjectiveTimeParams(ctypes.Structure):
+    """struct mtg_objective_time_params (include/mtg.h)."""
+    _fields_ = [("objective", ctypes.c_int32), ("derivative_to_optimize", ctypes.c_int32),
+                ("time_penalty", ctypes.c_double), ("w_c", ctypes.c_double), ("use_soft_constraints", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
 
 
 class ObjectiveParts(ctypes.Structure):
@@ -168,6 +175,21 @@ _SIGNATURES = {
                                                        ctypes.c_int, _c_dp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                                        ctypes.POINTER(SoftConstraintParams), _c_dp, _c_dp,
                                                        ctypes.c_double, _c_dp, _c_dp, _c_dp]),
+    "mtg_objective_time_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int64, _c_dp, _c_dp, _c_dp, ctypes.c_int64,
+                                                ctypes.POINTER(ObjectiveTimeParams), _c_dp, ctypes.POINTER(SdfGrid),
+                                                ctypes.POINTER(CollisionParams), ctypes.POINTER(SoftConstraintParams),
+                                                _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                                ctypes.POINTER(ObjectiveParts), _c_dp, ctypes.c_uint]),
+    "mtg_host_objective_time_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _c_dp,
+                                                     _c_dp, _c_dp, ctypes.c_int64, ctypes.POINTER(ObjectiveTimeParams),
+                                                     _c_dp, ctypes.POINTER(SdfGrid), ctypes.POINTER(CollisionParams),
+                                                     ctypes.POINTER(SoftConstraintParams), _c_dp, _c_dp, _c_dp, _c_dp,
+                                                     _c_dp, _c_dp, _c_dp, _c_dp, ctypes.POINTER(ObjectiveParts), _c_dp,
+                                                     ctypes.c_int]),
+    "mtg_host_objective_time_bounds_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                            _c_dp, ctypes.c_int, _c_dp, ctypes.c_int64, ctypes.c_double,
+                                                            _c_dp, _c_dp, _c_dp]),
     "mtg_time_jacobian_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_int64, _c_dp, _c_dp, ctypes.c_int, _c_dp,
                                                ctypes.c_double, _c_dp, _c_dp, ctypes.c_uint]),

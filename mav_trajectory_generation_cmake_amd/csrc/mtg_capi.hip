@@ -225,7 +225,7 @@ class Staged {
 
  private:
   static constexpr unsigned kIn = 1, kOut = 2;
-  static constexpr int kMax = 16;  // (the objective stages 11)
+  static constexpr int kMax = 16;  // (mtg_objective_time_batch stages 14)
   struct Rec {
     void* dev;   // the caller's T* variable
     void* host;
@@ -1365,6 +1365,208 @@ int mtg_objective_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const 
     for (const auto& q : pc)
       if (q.dst && q.have && q.bytes)
         MTG_HIP_TRY(ctx, hipMemcpyAsync(q.dst, ws + q.off, q.bytes, out_kind, ctx->stream));
+  }
+  return st.finish();
+}
+
+// The two gradient-free objectives in the segment times.  Launch sequence on the context's stream, no
+// host synchronisation in between:
+//   objective 3: times-unpack | solve (flags 0) | assemble | [soft] | [collision at coeff_times] | combine
+//   objective 4: unpack | cost | [soft] | [vertex map] | combine
+// As in mtg_objective_batch the component LAUNCHERS are called and intermediates live in ctx->workspace.
+int mtg_objective_time_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* values,
+                             const uint8_t* fixed_mask, const double* x, int64_t x_stride,
+                             const mtg_objective_time_params* params, const double* coeff_times,
+                             const mtg_sdf_grid* grid, const mtg_collision_params* collision,
+                             const mtg_soft_constraint_params* constraints, double* cost_out,
+                             double* weighted_costs_out, uint8_t* collision_out, double* constraint_values_out,
+                             mtg_extremum* maxima_out, double* free_out, double* coeffs_out,
+                             mtg_objective_state* state, const mtg_objective_parts* parts, int32_t* status,
+                             unsigned flags) {
+  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
+  if (!params) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "params are required");
+  const int obj = params->objective;
+  if (obj != MTG_OBJECTIVE_TIME && obj != MTG_OBJECTIVE_TIME_AND_CONSTRAINTS)
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "objective must be MTG_OBJECTIVE_TIME or MTG_OBJECTIVE_TIME_AND_CONSTRAINTS");
+  if (params->reserved != 0) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "reserved must be 0");
+  const bool solve = obj == MTG_OBJECTIVE_TIME;
+  const bool with_coll = solve && params->w_c > 0.0;
+  const bool with_soft = params->use_soft_constraints != 0;
+  const bool with_max = with_soft || constraint_values_out || maxima_out;  // the maxima search runs
+  const int r = params->derivative_to_optimize;
+  int rc = check_shape(ctx, N, D, K, r, batch);
+  if (rc != MTG_OK) return rc;
+  if (with_coll) {
+    rc = check_collision(ctx, N, D, K, batch, grid, collision, "w_c > 0 needs grid and collision params");
+    if (rc != MTG_OK) return rc;
+    if (!coeff_times) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "w_c > 0 needs coeff_times");
+  } else if (D > 4 || grid || collision || coeff_times) {
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT,
+                     "without a collision term (objective 4, or w_c <= 0) 1 <= D <= 4 and grid, collision, coeff_times are NULL");
+  }
+  int C = 0;
+  if (with_max) {
+    if (N < 6) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "the soft-constraint search needs N >= 6");
+    rc = check_soft_params(ctx, N, constraints, "constraints with 1 <= n_constraints <= 8 are required");
+    if (rc != MTG_OK) return rc;
+    C = constraints->n_constraints;
+  }
+  if (parts && (parts->dJd_dt || parts->dJc_dt || parts->grad_d || parts->grad_c || parts->grad_sc))
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "the gradient fields of parts must be NULL (these objectives have no gradient)");
+  if (x_stride < 0) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "x_stride must be >= 0");
+  if (batch == 0) return MTG_OK;
+  if (!values || !fixed_mask || !cost_out || !x || (with_coll && !grid->distance))
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "values, fixed_mask, x, cost_out (w_c > 0: grid->distance) are required");
+  const int V = K + 1, h = N / 2;
+  const bool dev = flags & MTG_FLAG_DEVICE_PTRS;
+  if (!dev) {  // the longest row must fit (a device-pointer call checks per trajectory in the unpack kernels)
+    int64_t longest = K;
+    for (int64_t b = 0; !solve && b < batch; ++b)
+      longest = std::max<int64_t>(longest, K + (int64_t)D * mtg::objective_n_free(fixed_mask + b * V, V, h));
+    if (x_stride < longest) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "x_stride is shorter than the longest row");
+  }
+  const bool with_map = !solve && coeffs_out;
+  if ((!solve && mtg::cost_lds_bytes(N, D, K) > 64 * 1024) || (with_coll && mtg::collision_lds_bytes(N, K) > 64 * 1024) ||
+      (with_max && mtg::soft_constraint_threads(N, D, K, C) == 0) || (with_map && !mtg::vertex_map_fits(N, D, K)) ||
+      batch > 0x7fffffff ||
+      (double)batch * (double)std::max<int64_t>(std::max<int64_t>((int64_t)V * h * D, (int64_t)K * D * N), x_stride) > 5e11)
+    return set_error(ctx, MTG_ERR_TOO_LARGE, "a component's per-trajectory working set exceeds LDS (reduce K), or the batch is too large");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+  // ---- workspace: every intermediate of the call (an output the caller asked for is written in place)
+  const size_t nB = (size_t)batch;
+  const size_t b_vv = sizeof(double) * nB * V * h * D, b_T = sizeof(double) * nB * K, b_s = sizeof(double) * nB,
+               b_free = sizeof(double) * nB * D * V * h, b_co = sizeof(double) * nB * K * D * N, b_i = sizeof(int32_t) * nB,
+               b_mx = sizeof(mtg_extremum) * nB * C;
+  const bool dlx = solve && mtg::solve_kernel(N, D, K, 0, r, batch) == MTG_KERNEL_DLX;
+  size_t woff = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = woff;
+    woff = align_up(woff + bytes);
+    return o;
+  };
+  const size_t w_vv = take(b_vv), w_T = take(b_T), w_ones = take(solve ? 0 : sizeof(double) * K), w_ct = take(b_s),
+               w_Jc = take(b_s), w_Jsc = take(b_s), w_Jt = take(b_s), w_free = take(solve && !free_out ? b_free : 0),
+               w_co = take(solve && !coeffs_out ? b_co : 0), w_mx = take(with_max && !maxima_out ? b_mx : 0),
+               w_coll = take(nB), w_nf = take(b_i), w_su = take(b_i), w_sv = take(b_i), w_sc = take(b_i), w_ss = take(b_i),
+               w_dlx = take(dlx ? mtg::dlx_workspace_bytes(N, D, K, batch) : 0);
+  MTG_HIP_TRY(ctx, ensure(&ctx->workspace, &ctx->workspace_bytes, std::max<size_t>(woff, 256)));
+  char* ws = static_cast<char*>(ctx->workspace);
+  auto wd = [&](size_t o) { return reinterpret_cast<double*>(ws + o); };
+  auto wi = [&](size_t o) { return reinterpret_cast<int32_t*>(ws + o); };
+
+  // ---- staging of a host-pointer call (the parts are copied out of the workspace)
+  const double *d_x, *d_vals, *d_ctimes;
+  const uint8_t* d_mask;
+  const float* d_grid;
+  double *d_cost, *d_w, *d_cv, *d_free, *d_co;
+  mtg_extremum* d_max;
+  uint8_t* d_coll;
+  mtg_objective_state* d_state;
+  int32_t* d_stat;
+  Staged st(ctx, flags);
+  st.in(&d_x, x, sizeof(double) * nB * (size_t)x_stride);
+  st.in(&d_vals, values, b_vv);
+  st.in(&d_mask, fixed_mask, nB * V);
+  st.in(&d_ctimes, coeff_times, with_coll ? b_T : 0);
+  st.in(&d_grid, with_coll ? grid->distance : nullptr, with_coll ? grid_bytes(*grid) : 0);
+  st.out(&d_cost, cost_out, b_s);
+  st.out(&d_w, weighted_costs_out, 4 * b_s);
+  st.out(&d_coll, collision_out, nB);
+  st.out(&d_cv, constraint_values_out, sizeof(double) * nB * C);
+  st.out(&d_max, maxima_out, b_mx);
+  st.out(&d_free, free_out, b_free);
+  st.out(&d_co, coeffs_out, b_co);
+  st.inout(&d_state, state, sizeof(mtg_objective_state) * nB);
+  st.out(&d_stat, status, b_i);
+  rc = st.upload();
+  if (rc != MTG_OK) return rc;
+
+  // ---- the launches
+  double* p_free = d_free ? d_free : (solve ? wd(w_free) : nullptr);
+  double* p_co = d_co ? d_co : (solve ? wd(w_co) : nullptr);
+  mtg_extremum* p_max = d_max ? d_max : (with_max ? reinterpret_cast<mtg_extremum*>(ws + w_mx) : nullptr);
+  uint8_t* p_coll = reinterpret_cast<uint8_t*>(ws + w_coll);
+  MTG_HIP_TRY(ctx, time_begin(ctx, false));
+  if (solve) {
+    mtg::ObjectiveTimesUnpackArgs ta{d_x, wd(w_T), wi(w_su), batch, x_stride, K};
+    MTG_HIP_TRY(ctx, mtg::launch_objective_times_unpack(ta, ctx->stream));
+    MTG_HIP_TRY(ctx, hipMemsetAsync(p_free, 0, b_free, ctx->stream));  // entries beyond n_free stay zero
+    mtg::SolveArgs sa{};
+    sa.values = d_vals;
+    sa.mask = d_mask;
+    sa.times = wd(w_T);
+    sa.coeffs = p_co;
+    sa.free_out = p_free;
+    sa.n_free_out = wi(w_nf);
+    sa.cost_out = wd(w_ct);
+    sa.status = wi(w_sv);
+    sa.B = batch;
+    sa.K = K;
+    sa.D = D;
+    sa.r = r;
+    sa.n_cand = 1;
+    if (dlx) {
+      sa.work = wd(w_dlx);
+      sa.work_bytes = (int64_t)mtg::dlx_workspace_bytes(N, D, K, batch);
+    }
+    MTG_HIP_TRY(ctx, mtg::launch_solve(N, sa, ctx->stream, 0));
+    mtg::ObjectiveAssembleArgs aa{d_vals, d_mask, p_free, wd(w_vv), batch, V, h, D};
+    MTG_HIP_TRY(ctx, mtg::launch_objective_assemble(aa, ctx->stream));
+  } else {
+    mtg::ObjectiveUnpackArgs ua{d_x, d_vals, d_mask, nullptr, wd(w_vv), wd(w_T), wi(w_nf), wi(w_su), wd(w_ones),
+                                batch, x_stride, K, V, h, D};
+    MTG_HIP_TRY(ctx, mtg::launch_objective_unpack(ua, ctx->stream));
+    MTG_HIP_TRY(ctx, mtg::launch_cost_at_times(N, r, wd(w_vv), d_mask, wd(w_T), wd(w_ones), wd(w_ct), nullptr, batch, K, D,
+                                               1, ctx->stream));
+  }
+  if (with_max)
+    MTG_HIP_TRY(ctx, mtg::launch_soft_constraint_cost(N, wd(w_vv), d_mask, wd(w_T), *constraints, wd(w_Jsc), nullptr, p_max,
+                                                      wi(w_ss), batch, K, D, ctx->stream));
+  if (with_coll)
+    MTG_HIP_TRY(ctx, mtg::launch_collision_cost(N, wd(w_vv), d_mask, wd(w_T), *grid, d_grid, *collision, wd(w_Jc), nullptr,
+                                                p_coll, nullptr, wi(w_sc), batch, K, ctx->stream, d_ctimes));
+  if (with_map) MTG_HIP_TRY(ctx, mtg::launch_vertex_map(true, N, wd(w_vv), wd(w_T), d_co, batch, K, D, ctx->stream));
+  mtg::ObjectiveTimeCombineArgs ca{};
+  ca.cost_traj = wd(w_ct);
+  ca.J_c = with_coll ? wd(w_Jc) : nullptr;
+  ca.J_sc = with_soft ? wd(w_Jsc) : nullptr;
+  ca.times = wd(w_T);
+  ca.collision = with_coll ? p_coll : nullptr;
+  ca.st_unpack = wi(w_su);
+  ca.st_solve = solve ? wi(w_sv) : nullptr;
+  ca.st_soft = with_max ? wi(w_ss) : nullptr;
+  ca.st_collision = with_coll ? wi(w_sc) : nullptr;
+  ca.maxima = p_max;
+  ca.x = d_x;
+  ca.n_free = wi(w_nf);
+  for (int c = 0; c < C; ++c) ca.limit[c] = constraints->limit[c];
+  ca.C = C;
+  ca.cost_out = d_cost;
+  ca.weighted = d_w;
+  ca.J_t_out = wd(w_Jt);
+  ca.constraint_values = d_cv;
+  ca.free_out = d_free;
+  ca.coeffs_out = d_co;
+  ca.maxima_out = d_max;
+  ca.collision_out = d_coll;
+  ca.state = d_state;
+  ca.status = d_stat;
+  ca.B = batch;
+  ca.x_stride = x_stride;
+  ca.K = K, ca.V = V, ca.h = h, ca.D = D, ca.N = N;
+  ca.rule = mtg::ObjectiveTimeRule{obj, params->time_penalty, params->w_c};
+  MTG_HIP_TRY(ctx, mtg::launch_objective_time_combine(ca, ctx->stream));
+  MTG_HIP_TRY(ctx, time_end(ctx));
+
+  // ---- the parts (from the workspace) and, for host pointers, the outputs
+  if (parts) {
+    const hipMemcpyKind out_kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const struct { double* dst; size_t off; bool have; } pc[] = {{parts->J_d, w_ct, !solve}, {parts->J_c, w_Jc, with_coll},
+                                                                  {parts->J_sc, w_Jsc, with_max}, {parts->J_t, w_Jt, true}};
+    for (const auto& q : pc)
+      if (q.dst && q.have) MTG_HIP_TRY(ctx, hipMemcpyAsync(q.dst, ws + q.off, b_s, out_kind, ctx->stream));
   }
   return st.finish();
 }

@@ -20,6 +20,9 @@
 // replace the segment's coefficients in LDS (no longer needed); the cost partial sums are reduced
 // the same way at the end.  No atomics: a trajectory's result depends on nothing but its own data.
 // Last, A(T_i)^-T per (segment, axis) column and the free-order packing, as cost_at_times_kernel.
+// With coefficient times (mtg_objective_time_batch's stale L_) a third instantiation forms the
+// coefficients at those times and walks to `times`; the two kernels of mtg_collision_cost_batch are
+// the instantiations without it, untouched.
 #include "mtg_collision_common.h"
 #include "mtg_device.h"
 
@@ -29,6 +32,7 @@ struct CollisionArgs {
   const double* values;  // [B][V][h][3] all derivatives
   const uint8_t* mask;   // [B][V] (gradient only)
   const double* times;   // [B][K]
+  const double* coeff_times;  // [B][K] (nullable): the coefficients' times where they differ from the walk's
   CollisionMap map;
   CollisionPot pot;
   double dt;
@@ -53,7 +57,8 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-template <int N, bool GRAD>
+// STALE: the coefficients are formed at a.coeff_times, the walk reads a.times (cost only)
+template <int N, bool GRAD, bool STALE = false>
 __global__ __launch_bounds__(64) void collision_kernel(CollisionArgs a) {
   constexpr int H = N / 2;
   constexpr unsigned HM = (1u << H) - 1u;
@@ -74,6 +79,10 @@ __global__ __launch_bounds__(64) void collision_kernel(CollisionArgs a) {
     const double T = a.times[b * K + i];
     tl[i] = T;
     bad |= !(T > 0.0 && T <= DBL_MAX) || !(T / a.dt <= kCollisionMaxSegmentSamples);
+    if (STALE) {
+      const double Tc = a.coeff_times[b * K + i];
+      bad |= !(Tc > 0.0 && Tc <= DBL_MAX);
+    }
   }
   if (lane < 3) ps[lane * kPosStride] = 0.0;
   __syncthreads();
@@ -91,7 +100,7 @@ __global__ __launch_bounds__(64) void collision_kernel(CollisionArgs a) {
   cdouble* Ai1 = (cdouble*)(c_a1inv + MTG_A1INV_OFF(N));
   for (int j = lane; j < cols; j += 64) {
     const int i = j / 3, d = j - i * 3;
-    const double T = tl[i];
+    const double T = STALE ? a.coeff_times[b * K + i] : tl[i];
     double s[H];
     s[0] = 1.0;
 #pragma unroll
@@ -297,7 +306,9 @@ hipError_t launch_collision_n(const CollisionArgs& a, bool grad, hipStream_t str
   const size_t lds = collision_lds_bytes(N, a.K);
   if (lds > kMaxLdsPerBlock) return hipErrorInvalidValue;
   if (a.B == 0) return hipSuccess;
-  if (grad) launch_kernel((collision_kernel<N, true>), dim3((unsigned)a.B), dim3(64), lds, stream, a);
+  if (a.coeff_times && grad) return hipErrorInvalidValue;  // (the stale-L_ gradient is not built)
+  if (a.coeff_times) launch_kernel((collision_kernel<N, false, true>), dim3((unsigned)a.B), dim3(64), lds, stream, a);
+  else if (grad) launch_kernel((collision_kernel<N, true>), dim3((unsigned)a.B), dim3(64), lds, stream, a);
   else launch_kernel((collision_kernel<N, false>), dim3((unsigned)a.B), dim3(64), lds, stream, a);
   return hipGetLastError();
 }
@@ -312,11 +323,12 @@ size_t collision_lds_bytes(int N, int K) {
 hipError_t launch_collision_cost(int N, const double* values, const uint8_t* mask, const double* times,
                                  const mtg_sdf_grid& grid, const float* distance, const mtg_collision_params& p,
                                  double* cost, double* grad, uint8_t* collision, int32_t* n_evaluated, int32_t* status,
-                                 int64_t B, int K, hipStream_t stream) {
+                                 int64_t B, int K, hipStream_t stream, const double* coeff_times) {
   CollisionArgs a;
   a.values = values;
   a.mask = mask;
   a.times = times;
+  a.coeff_times = coeff_times;
   a.map = CollisionMap{distance, grid.nx, grid.ny, grid.nz, {grid.origin[0], grid.origin[1], grid.origin[2]},
                        grid.resolution, grid.oob_distance};
   a.pot = CollisionPot{p.map_resolution, p.epsilon, p.robot_radius, p.coll_pot_multiplier,

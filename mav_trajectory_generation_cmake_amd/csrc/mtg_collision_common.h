@@ -146,4 +146,15 @@ MTG_HD double collision_potential_at(const CollisionMap& m, const CollisionPot& 
   return c;
 }
 
+#if !defined(__HIPCC__)
+// mtg_host_collision_cost_batch (mtg_host_collision.cpp) with the coefficients formed at coeff_times
+// [B][K] while the loop reads `times`: the stale L_ of objectiveFunctionTime (mtg.h,
+// mtg_objective_time_batch).  Cost only.  coeff_times == nullptr is the exported function; an entry
+// that is not positive and finite gives MTG_TRAJ_BAD_TIME.
+int host_collision_cost_coeff_times(int N, int D, int K, int64_t batch, const double* vertex_values,
+                                    const double* times, const double* coeff_times, const mtg_sdf_grid* grid,
+                                    const mtg_collision_params* params, double* cost_out, uint8_t* collision_out,
+                                    int32_t* n_evaluated_out, int32_t* status, int threads);
+#endif
+
 }  // namespace mtg

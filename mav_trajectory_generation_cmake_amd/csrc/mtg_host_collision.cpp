@@ -4,6 +4,8 @@
 // once per segment after the loop: A(T_i)^-T on the segment's accumulated coefficient-space
 // vector, then the (vertex, derivative) packing of mtg_cost_at_times_batch.  The per-position part
 // (map lookup, potential, central differences) is mtg_collision_common.h, shared with the kernel.
+// mtg::host_collision_cost_coeff_times is the same loop with the coefficients formed at other times
+// than the loop's (the stale L_ of objectiveFunctionTime, for mtg_host_objective_time_batch).
 // Plain C++ (no HIP).
 #include <algorithm>
 #include <cfloat>
@@ -26,14 +28,16 @@ struct Work {
   std::vector<double> acc;     // [K][3][N] per-segment coefficient-space vectors
 };
 
-void one(int N, int K, const double* values, const uint8_t* mask, const double* times, const mtg::CollisionMap& map,
-         const mtg::CollisionPot& pot, double dt, double* cost, double* grad, uint8_t* collision, int32_t* n_evaluated,
-         int32_t* status, Work& w) {
+// coeff_times (nullable): the times the coefficients are formed at, where they differ from the loop's
+void one(int N, int K, const double* values, const uint8_t* mask, const double* times, const double* coeff_times,
+         const mtg::CollisionMap& map, const mtg::CollisionPot& pot, double dt, double* cost, double* grad,
+         uint8_t* collision, int32_t* n_evaluated, int32_t* status, Work& w) {
   const int h = N / 2, V = K + 1, D = 3;
   bool bad = false;
   for (int i = 0; i < K; ++i) {
     const double T = times[i];
     if (!(T > 0.0 && T <= DBL_MAX) || !(T / dt <= mtg::kCollisionMaxSegmentSamples)) bad = true;
+    if (coeff_times && !(coeff_times[i] > 0.0 && coeff_times[i] <= DBL_MAX)) bad = true;
   }
   if (grad) std::fill(grad, grad + (size_t)D * V * h, 0.0);
   if (collision) *collision = 0;
@@ -44,7 +48,7 @@ void one(int N, int K, const double* values, const uint8_t* mask, const double* 
     return;
   }
   w.coeffs.resize((size_t)K * D * N);
-  mtg_host_coefficients_from_vertices_batch(N, D, K, 1, values, times, w.coeffs.data(), 1);
+  mtg_host_coefficients_from_vertices_batch(N, D, K, 1, values, coeff_times ? coeff_times : times, w.coeffs.data(), 1);
   if (grad) w.acc.assign((size_t)K * D * N, 0.0);
 
   double J = 0.0;
@@ -142,13 +146,9 @@ void one(int N, int K, const double* values, const uint8_t* mask, const double* 
   }
 }
 
-}  // namespace
-
-extern "C" int mtg_host_collision_cost_batch(int N, int D, int K, int64_t batch, const double* vertex_values,
-                                             const uint8_t* fixed_mask, const double* times, const mtg_sdf_grid* grid,
-                                             const mtg_collision_params* params, double* cost_out, double* grad_out,
-                                             uint8_t* collision_out, int32_t* n_evaluated_out, int32_t* status,
-                                             int threads) {
+int run(int N, int D, int K, int64_t batch, const double* vertex_values, const uint8_t* fixed_mask, const double* times,
+        const double* coeff_times, const mtg_sdf_grid* grid, const mtg_collision_params* params, double* cost_out,
+        double* grad_out, uint8_t* collision_out, int32_t* n_evaluated_out, int32_t* status, int threads) {
   if (N < 6 || N > 12 || (N % 2)) return MTG_ERR_UNSUPPORTED_N;
   if (D != 3) return MTG_ERR_INVALID_ARGUMENT;
   if (K < 1 || batch < 0) return MTG_ERR_SIZE_MISMATCH;
@@ -169,10 +169,29 @@ extern "C" int mtg_host_collision_cost_batch(int N, int D, int K, int64_t batch,
   mtg::run_threads(batch, threads, [&](int64_t b0, int64_t b1) {
     Work w;
     for (int64_t b = b0; b < b1; ++b)
-      one(N, K, vertex_values + b * (int64_t)V * h * D, fixed_mask ? fixed_mask + b * V : nullptr, times + b * K, map, pot,
-          dt, cost_out + b, grad_out ? grad_out + b * (int64_t)D * V * h : nullptr,
-          collision_out ? collision_out + b : nullptr, n_evaluated_out ? n_evaluated_out + b : nullptr,
-          status ? status + b : nullptr, w);
+      one(N, K, vertex_values + b * (int64_t)V * h * D, fixed_mask ? fixed_mask + b * V : nullptr, times + b * K,
+          coeff_times ? coeff_times + b * K : nullptr, map, pot, dt, cost_out + b,
+          grad_out ? grad_out + b * (int64_t)D * V * h : nullptr, collision_out ? collision_out + b : nullptr,
+          n_evaluated_out ? n_evaluated_out + b : nullptr, status ? status + b : nullptr, w);
   });
   return MTG_OK;
+}
+
+}  // namespace
+
+extern "C" int mtg_host_collision_cost_batch(int N, int D, int K, int64_t batch, const double* vertex_values,
+                                             const uint8_t* fixed_mask, const double* times, const mtg_sdf_grid* grid,
+                                             const mtg_collision_params* params, double* cost_out, double* grad_out,
+                                             uint8_t* collision_out, int32_t* n_evaluated_out, int32_t* status,
+                                             int threads) {
+  return run(N, D, K, batch, vertex_values, fixed_mask, times, nullptr, grid, params, cost_out, grad_out, collision_out,
+             n_evaluated_out, status, threads);
+}
+
+int mtg::host_collision_cost_coeff_times(int N, int D, int K, int64_t batch, const double* vertex_values,
+                                         const double* times, const double* coeff_times, const mtg_sdf_grid* grid,
+                                         const mtg_collision_params* params, double* cost_out, uint8_t* collision_out,
+                                         int32_t* n_evaluated_out, int32_t* status, int threads) {
+  return run(N, D, K, batch, vertex_values, nullptr, times, coeff_times, grid, params, cost_out, nullptr, collision_out,
+             n_evaluated_out, status, threads);
 }

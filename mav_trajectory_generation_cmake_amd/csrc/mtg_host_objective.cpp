@@ -5,6 +5,10 @@
 // getCostAndGradientTime :2155-2243); the weighting, raise and state rules are
 // mtg_objective_common.h, shared with the kernels.  Also mtg_host_objective_bounds_batch
 // (setFreeEndpointDerivativeHardConstraints :2518-2564, the time bounds and initial step :646-692).
+// And mtg_host_objective_time_batch, the two gradient-free objectives in the segment times
+// (objectiveFunctionTime :765-832, objectiveFunctionTimeAndConstraints :835-906) composed of the host
+// solve, the host soft-constraint path, the host collision loop with coefficient times and the same
+// derivative term, with mtg_host_objective_time_bounds_batch (:248-276, :551-562).
 // Plain C++ (no HIP).
 #include <algorithm>
 #include <cfloat>
@@ -14,6 +18,7 @@
 #include <vector>
 
 #include "mtg.h"
+#include "mtg_collision_common.h"
 #include "mtg_host_threads.h"
 #include "mtg_objective_common.h"
 
@@ -307,6 +312,185 @@ extern "C" int mtg_host_objective_bounds_batch(int N, int D, int K, int64_t batc
       if (lower) lower[b * x_stride + j] = !in_row ? 0.0 : j < nt ? 0.1 : lo[j - nt];
       if (upper) upper[b * x_stride + j] = !in_row ? 0.0 : j < nt ? inf : up[j - nt];
       if (initial_step) initial_step[b * x_stride + j] = in_row ? initial_stepsize_rel * std::abs(x[b * x_stride + j]) : 0.0;
+    }
+  }
+  return MTG_OK;
+}
+
+// ---- mtg_objective_time_batch on the host: objectiveFunctionTime (nl_impl:765-832) and
+// objectiveFunctionTimeAndConstraints (:835-906), in the launch order of the device call.
+extern "C" int mtg_host_objective_time_batch(int N, int D, int K, int64_t batch, const double* values,
+                                             const uint8_t* fixed_mask, const double* x, int64_t x_stride,
+                                             const mtg_objective_time_params* params, const double* coeff_times,
+                                             const mtg_sdf_grid* grid, const mtg_collision_params* collision,
+                                             const mtg_soft_constraint_params* constraints, double* cost_out,
+                                             double* weighted_costs_out, uint8_t* collision_out,
+                                             double* constraint_values_out, mtg_extremum* maxima_out, double* free_out,
+                                             double* coeffs_out, mtg_objective_state* state,
+                                             const mtg_objective_parts* parts, int32_t* status, int threads) {
+  if (!params) return MTG_ERR_INVALID_ARGUMENT;
+  const int obj = params->objective;
+  if (obj != MTG_OBJECTIVE_TIME && obj != MTG_OBJECTIVE_TIME_AND_CONSTRAINTS) return MTG_ERR_INVALID_ARGUMENT;
+  if (params->reserved != 0) return MTG_ERR_INVALID_ARGUMENT;
+  const bool solve = obj == MTG_OBJECTIVE_TIME;
+  const bool with_coll = solve && params->w_c > 0.0;
+  const bool with_soft = params->use_soft_constraints != 0;
+  const bool with_max = with_soft || constraint_values_out || maxima_out;
+  const int r = params->derivative_to_optimize;
+  if (N < 2 || N > 12 || (N % 2)) return MTG_ERR_UNSUPPORTED_N;
+  const int h = N / 2, V = K + 1;
+  if (r < 0 || r > h - 1) return MTG_ERR_BAD_DERIVATIVE;
+  if (K < 1 || D < 1 || batch < 0) return MTG_ERR_SIZE_MISMATCH;
+  if (with_coll) {
+    if (N < 6) return MTG_ERR_UNSUPPORTED_N;
+    if (D != 3 || !grid || !collision || !coeff_times) return MTG_ERR_INVALID_ARGUMENT;
+  } else if (D > 4 || grid || collision || coeff_times) {
+    return MTG_ERR_INVALID_ARGUMENT;
+  }
+  if (with_max && (!constraints || N < 6)) return MTG_ERR_INVALID_ARGUMENT;
+  if (parts && (parts->dJd_dt || parts->dJc_dt || parts->grad_d || parts->grad_c || parts->grad_sc))
+    return MTG_ERR_INVALID_ARGUMENT;
+  if (x_stride < 0) return MTG_ERR_INVALID_ARGUMENT;
+  if (batch == 0) return MTG_OK;
+  if (!values || !fixed_mask || !cost_out || !x) return MTG_ERR_INVALID_ARGUMENT;
+  const size_t nB = (size_t)batch, per = (size_t)V * h * D, gper = (size_t)D * V * h, cper = (size_t)K * D * N;
+  std::vector<int32_t> n_free(nB);
+  for (int64_t b = 0; b < batch; ++b) {
+    n_free[b] = mtg::objective_n_free(fixed_mask + b * V, V, h);
+    if (x_stride < K + (solve ? 0 : (int64_t)D * n_free[b])) return MTG_ERR_INVALID_ARGUMENT;
+  }
+  const int C = with_max ? constraints->n_constraints : 0;
+
+  // ---- the times, and the trajectory at x
+  std::vector<double> T(nB * K), vv(nB * per), ct(nB), fr(solve ? nB * gper : 0), co((solve || coeffs_out) ? nB * cper : 0);
+  std::vector<int32_t> st(nB, 0), st_v(nB, 0), st_c(nB, 0), st_s(nB, 0);
+  for (int64_t b = 0; b < batch; ++b)
+    for (int i = 0; i < K; ++i) {
+      T[b * K + i] = x[b * x_stride + i];
+      if (mtg::objective_time_bad(T[b * K + i])) st[b] |= MTG_TRAJ_BAD_TIME;
+    }
+  int rc = MTG_OK;
+  if (solve) {
+    rc = mtg_host_solve_linear_batch(N, D, K, r, batch, values, fixed_mask, T.data(), co.data(), fr.data(), nullptr,
+                                     ct.data(), st_v.data(), threads);
+    if (rc != MTG_OK) return rc;
+  }
+  for (int64_t b = 0; b < batch; ++b) {
+    const uint8_t* mask = fixed_mask + b * V;
+    for (int v = 0; v < V; ++v)
+      for (int k = 0; k < h; ++k)
+        for (int d = 0; d < D; ++d) {
+          const size_t e = ((size_t)v * h + k) * D + d;
+          const int fi = mtg::objective_free_index(mask, v, k, h);
+          vv[b * per + e] = ((mask[v] >> k) & 1u) ? values[b * per + e]
+                            : solve               ? fr[b * gper + (size_t)d * V * h + fi]
+                                                  : x[b * x_stride + K + (int64_t)d * n_free[b] + fi];
+        }
+  }
+
+  // ---- the parts
+  std::vector<double> J_c(nB, 0.0), J_sc(nB, 0.0), J_t(nB, 0.0);
+  std::vector<uint8_t> coll(nB, 0);
+  std::vector<mtg_extremum> mx((size_t)nB * C);
+  if (!solve) {
+    mtg::run_threads(batch, threads, [&](int64_t b0, int64_t b1) {
+      for (int64_t b = b0; b < b1; ++b)
+        ct[b] = (st[b] & MTG_TRAJ_BAD_TIME) ? std::numeric_limits<double>::quiet_NaN()
+                                            : derivative_cost(N, D, K, r, vv.data() + b * per, T.data() + b * K, nullptr);
+    });
+    if (coeffs_out) rc = mtg_host_coefficients_from_vertices_batch(N, D, K, batch, vv.data(), T.data(), co.data(), threads);
+  }
+  if (rc == MTG_OK && with_max)
+    rc = mtg_host_soft_constraint_cost_batch(N, D, K, batch, vv.data(), nullptr, T.data(), constraints, J_sc.data(),
+                                             nullptr, mx.data(), st_s.data(), threads);
+  if (rc == MTG_OK && with_coll)
+    rc = mtg::host_collision_cost_coeff_times(N, D, K, batch, vv.data(), T.data(), coeff_times, grid, collision,
+                                              J_c.data(), coll.data(), nullptr, st_c.data(), threads);
+  if (rc != MTG_OK) return rc;
+
+  // ---- combine (the rule of mtg_objective_common.h, as the combine kernel applies it)
+  const mtg::ObjectiveTimeRule rule{obj, params->time_penalty, params->w_c};
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (int64_t b = 0; b < batch; ++b) {
+    const int stb = st[b] | st_v[b] | st_s[b] | st_c[b];
+    const bool err = (stb & MTG_TRAJ_ERROR_MASK) != 0;
+    const int nf = n_free[b];
+    if (status) status[b] = stb;
+    J_t[b] = mtg::objective_total_time(T.data() + b * K, K);
+    if (free_out)
+      for (size_t j = 0; j < gper; ++j) {
+        const size_t d = j / ((size_t)V * h), i = j % ((size_t)V * h);
+        free_out[b * gper + j] = err     ? nan
+                                 : solve ? fr[b * gper + j]
+                                         : ((int)i < nf ? x[b * x_stride + K + (int64_t)d * nf + (int64_t)i] : 0.0);
+      }
+    if (coeffs_out)
+      for (size_t j = 0; j < cper; ++j) coeffs_out[b * cper + j] = err ? nan : co[b * cper + j];
+    for (int c = 0; c < C; ++c) {
+      if (constraint_values_out)
+        constraint_values_out[b * C + c] = err ? nan : mx[b * C + c].value - constraints->limit[c];
+      if (maxima_out) maxima_out[b * C + c] = err ? mtg_extremum{nan, nan, 0, 0} : mx[b * C + c];
+    }
+    if (err) {
+      cost_out[b] = nan;
+      if (weighted_costs_out)
+        for (int q = 0; q < 4; ++q) weighted_costs_out[4 * b + q] = nan;
+      if (collision_out) collision_out[b] = 0;
+      continue;
+    }
+    mtg_objective_state in = {};
+    if (state) in = state[b];
+    mtg_objective_state out;
+    double w4[4];
+    cost_out[b] = mtg::objective_time_combine_cost(rule, ct[b], J_c[b], with_soft ? J_sc[b] : 0.0, J_t[b], in, &out, w4);
+    if (weighted_costs_out)
+      for (int q = 0; q < 4; ++q) weighted_costs_out[4 * b + q] = w4[q];
+    if (collision_out) collision_out[b] = coll[b] ? 1 : 0;
+    if (state) state[b] = out;
+  }
+  if (parts) {
+    auto put = [](double* dst, const std::vector<double>& src, bool have) {
+      if (dst && have) std::copy(src.begin(), src.end(), dst);
+    };
+    put(parts->J_d, ct, !solve);
+    put(parts->J_c, J_c, with_coll);
+    put(parts->J_sc, J_sc, with_max);
+    put(parts->J_t, J_t, true);
+  }
+  return MTG_OK;
+}
+
+extern "C" int mtg_host_objective_time_bounds_batch(int N, int D, int K, int64_t batch, const uint8_t* fixed_mask,
+                                                    int objective, const double* x, int64_t x_stride,
+                                                    double initial_stepsize_rel, double* lower, double* upper,
+                                                    double* initial_step) {
+  if (N < 2 || N > 12 || (N % 2)) return MTG_ERR_UNSUPPORTED_N;
+  const int h = N / 2, V = K + 1;
+  if (K < 1 || D < 1 || batch < 0) return MTG_ERR_SIZE_MISMATCH;
+  const bool times_only = objective == MTG_OBJECTIVE_TIME;
+  if ((!times_only && objective != MTG_OBJECTIVE_TIME_AND_CONSTRAINTS) || x_stride < 0) return MTG_ERR_INVALID_ARGUMENT;
+  if (batch == 0) return MTG_OK;
+  if (!x || (!times_only && !fixed_mask)) return MTG_ERR_INVALID_ARGUMENT;
+  for (int64_t b = 0; b < batch; ++b) {
+    const int64_t len = K + (times_only ? 0 : (int64_t)D * mtg::objective_n_free(fixed_mask + b * V, V, h));
+    if (len > x_stride) return MTG_ERR_INVALID_ARGUMENT;
+    for (int64_t j = 0; j < x_stride; ++j) {
+      const double xv = x[b * x_stride + j];
+      double lo = 0.0, up = 0.0, step = 0.0;
+      if (j < len && times_only) {  // nl_impl:248-256, :273-276
+        step = initial_stepsize_rel * xv;
+        up = xv * 2.0;
+        lo = 0.1;
+      } else if (j < len) {  // nl_impl:551-562
+        const double abs_x = std::abs(xv);
+        step = initial_stepsize_rel * abs_x;
+        lo = -abs_x * 2;
+        up = abs_x * 2;
+        if (j < K) lo = 0.1;
+      }
+      if (lower) lower[b * x_stride + j] = lo;
+      if (upper) upper[b * x_stride + j] = up;
+      if (initial_step) initial_step[b * x_stride + j] = step;
     }
   }
   return MTG_OK;

@@ -88,12 +88,15 @@ hipError_t launch_cost_at_times(int N, int r, const double* values, const uint8_
                                 hipStream_t stream);
 
 // collision cost / gradient over a signed distance field (mtg_collision.hip); `distance` is the
-// device copy of grid.distance
+// device copy of grid.distance.  coeff_times [B][K] (nullable, cost only: hipErrorInvalidValue with
+// grad): the coefficients are formed at these times while the walk reads `times` (the stale L_ of
+// objectiveFunctionTime, mtg.h); an entry that is not positive and finite gives MTG_TRAJ_BAD_TIME.
+// nullptr launches the kernels of mtg_collision_cost_batch, unchanged.
 size_t collision_lds_bytes(int N, int K);
 hipError_t launch_collision_cost(int N, const double* values, const uint8_t* mask, const double* times,
                                  const mtg_sdf_grid& grid, const float* distance, const mtg_collision_params& p,
                                  double* cost, double* grad, uint8_t* collision, int32_t* n_evaluated, int32_t* status,
-                                 int64_t B, int K, hipStream_t stream);
+                                 int64_t B, int K, hipStream_t stream, const double* coeff_times = nullptr);
 
 // segment-time gradient of the collision cost (mtg_collision_time.hip); `distance` is the device copy
 // of grid.distance
@@ -149,6 +152,47 @@ struct ObjectiveCombineArgs {
 };
 hipError_t launch_objective_unpack(const ObjectiveUnpackArgs& a, hipStream_t stream);
 hipError_t launch_objective_combine(const ObjectiveCombineArgs& a, hipStream_t stream);
+
+// the kernels of mtg_objective_time_batch (mtg_objective.hip) that the component launchers do not
+// provide.  All pointers are device pointers.
+struct ObjectiveTimesUnpackArgs {  // objective 3: x -> times, the bad-time and row-too-short status
+  const double* x;  // [B][x_stride]
+  double* times;    // [B][K]; 1.0 for a row that does not fit x_stride (its x is not read)
+  int32_t* status;  // [B]
+  int64_t B, x_stride;
+  int K;
+};
+struct ObjectiveAssembleArgs {  // objective 3: values, fixed_mask and the solve's free_out -> vertex_values
+  const double* values;   // [B][V][h][D]
+  const uint8_t* mask;    // [B][V]
+  const double* free;     // [B][D][V*h]
+  double* vertex_values;  // [B][V][h][D]
+  int64_t B;
+  int V, h, D;
+};
+struct ObjectiveTimeCombineArgs {
+  const double* cost_traj;     // [B]: the solve's cost (objective 3) or J_d (objective 4)
+  const double *J_c, *J_sc;    // [B] (nullable: 0)
+  const double* times;         // [B][K]
+  const uint8_t* collision;    // [B] (nullable: 0)
+  const int32_t *st_unpack, *st_solve, *st_soft, *st_collision;  // [B] (all but st_unpack nullable)
+  const mtg_extremum* maxima;  // [B][C] as the soft-constraint kernel wrote them (nullable; may be maxima_out)
+  const double* x;             // [B][x_stride] and
+  const int32_t* n_free;       // [B]: objective 4's free_out (nullable otherwise)
+  double limit[8];
+  int C;
+  double *cost_out, *weighted, *J_t_out, *constraint_values, *free_out, *coeffs_out;  // (all but cost_out nullable)
+  mtg_extremum* maxima_out;
+  uint8_t* collision_out;
+  mtg_objective_state* state;
+  int32_t* status;
+  int64_t B, x_stride;
+  int K, V, h, D, N;
+  ObjectiveTimeRule rule;
+};
+hipError_t launch_objective_times_unpack(const ObjectiveTimesUnpackArgs& a, hipStream_t stream);
+hipError_t launch_objective_assemble(const ObjectiveAssembleArgs& a, hipStream_t stream);
+hipError_t launch_objective_time_combine(const ObjectiveTimeCombineArgs& a, hipStream_t stream);
 
 // vertex derivatives <-> coefficients (mtg_vertex.hip)
 bool vertex_map_fits(int N, int D, int K);

@@ -134,4 +134,52 @@ MTG_OBJ_HD double objective_total_time(const double* T, int K) {
 // a segment time the reference would CHECK-fail on
 MTG_OBJ_HD bool objective_time_bad(double T) { return !(T > 0.0 && T <= 1.7976931348623157e308); }
 
+// the fields of mtg_objective_time_params the combination of mtg_objective_time_batch reads, by value
+struct ObjectiveTimeRule {
+  int objective;
+  double time_penalty, w_c;
+};
+
+// cost, weighted costs [4] and the new state of one trajectory for objectiveFunctionTime (cost_traj: the
+// solve's cost) and objectiveFunctionTimeAndConstraints (cost_traj: J_d, halved here), mtg.h
+// "Semantics" of mtg_objective_time_batch; J_sc is 0 with the soft constraints off.
+MTG_OBJ_HD double objective_time_combine_cost(const ObjectiveTimeRule& p, double cost_traj, double J_c, double J_sc,
+                                              double J_t, const mtg_objective_state& in, mtg_objective_state* out,
+                                              double* weighted) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  mtg_objective_state s = in;
+  const double ctime = (J_t * J_t) * p.time_penalty;
+  const double cs = J_sc;
+  double cost, ct, cc = 0.0;
+  if (p.objective == MTG_OBJECTIVE_TIME) {
+    ct = cost_traj;
+    if (p.w_c > 0.0) cc = p.w_c * J_c;
+    cost = ((ct + cc) + ctime) + cs;
+    s.n_iterations++;
+    s.cost_trajectory = ct;
+    s.cost_collision = cc;
+    s.cost_time = ctime;
+    s.cost_soft_constraints = cs;
+    if (!s.iter0_done) {
+      s.total_cost_iter0 = cost;
+      s.iter0_done = 1;
+    }
+  } else {
+    ct = 0.5 * cost_traj;
+    cost = (ct + ctime) + cs;
+    s.n_iterations++;
+    s.cost_trajectory = ct;
+    s.cost_time = ctime;
+    s.cost_soft_constraints = cs;
+  }
+  weighted[0] = ct;
+  weighted[1] = cc;
+  weighted[2] = ctime;
+  weighted[3] = cs;
+  *out = s;
+  return cost;
+}
+
 }  // namespace mtg

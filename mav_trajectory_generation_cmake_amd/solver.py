@@ -372,6 +372,24 @@ class Context:
         return _objective_call(self, N, values, mask, x, params, times, grid, collision, soft, state, grad, parts,
                                asynchronous, None)
 
+    def objective_time_batch(self, N, values, mask, x, params, coeff_times=None, grid=None, collision=None,
+                             constraints=None, state=None, parts=False, constraint_values=False, maxima=False,
+                             free=False, coeffs=False, asynchronous=False):
+        """One evaluation of objectiveFunctionTime (objective 3) or objectiveFunctionTimeAndConstraints
+        (objective 4) per trajectory (include/mtg.h mtg_objective_time_batch): x [B][x_stride] holds the K
+        segment times (objective 4: then D blocks of n_free[b] free derivatives); values / mask are the
+        problem as solve_linear_batch reads it; params an ObjectiveTimeParams; coeff_times [B][K], grid
+        and collision iff objective 3 with w_c > 0 (the collision walk's coefficients are formed at
+        coeff_times: the reference's stale L_); constraints a SoftConstraintParams, needed with
+        use_soft_constraints, constraint_values or maxima.  numpy arrays or torch CUDA tensors, state and
+        asynchronous as in objective_batch.  Returns the keys of objective_batch (grad is None: these
+        objectives have none; parts=True gives J_d (objective 4), J_c, J_sc, J_t) plus
+        constraint_values [B][C] (maxima.value - limit: the hard inequality constraints' values), maxima
+        (as soft_constraint_cost_batch returns them), free [B][D][V*h] and coeffs [B][K][D][N], each
+        None unless requested."""
+        return _objective_time_call(self, N, values, mask, x, params, coeff_times, grid, collision, constraints, state,
+                                    parts, constraint_values, maxima, free, coeffs, asynchronous, None)
+
     def soft_constraint_cost_batch(self, N, vertex_values, times, params, mask=None, grad=False, asynchronous=False):
         """getCostAndGradientSoftConstraints for a batch (include/mtg.h mtg_soft_constraint_cost_batch):
         vertex_values [B][V][h][D] (all derivatives), times [B][K], params a SoftConstraintParams.  numpy
@@ -967,6 +985,119 @@ def host_objective_bounds_batch(N, D, K, mask, x, derivative_to_optimize, with_t
         N, D, K, B, _addr(mask), int(bool(with_times)), _addr(x), stride, int(derivative_to_optimize),
         int(bool(solve_with_position_constraint)), ctypes.byref(cp) if cp is not None else None, _addr(mn), _addr(mx),
         float(initial_stepsize_rel), _addr(lo), _addr(up), _addr(step)))
+    return lo, up, step
+
+
+class ObjectiveTimeParams:
+    """struct mtg_objective_time_params (include/mtg.h): objective 3 (objectiveFunctionTime) or 4
+    (objectiveFunctionTimeAndConstraints, the reference's default), time_penalty (reference default 500),
+    w_c (objective 3 only: the collision term exists iff w_c > 0) and use_soft_constraints."""
+
+    def __init__(self, objective, derivative_to_optimize, time_penalty=500.0, w_c=0.0, use_soft_constraints=True,
+                 reserved=0):
+        self.objective = int(objective)
+        self.derivative_to_optimize = int(derivative_to_optimize)
+        self.time_penalty = float(time_penalty)
+        self.w_c = float(w_c)
+        self.use_soft_constraints = bool(use_soft_constraints)
+        self.reserved = int(reserved)
+
+    def native(self):
+        return nat.ObjectiveTimeParams(self.objective, self.derivative_to_optimize, self.time_penalty, self.w_c,
+                                       int(self.use_soft_constraints), self.reserved)
+
+
+OBJECTIVE_TIME_PARTS = ("J_d", "J_c", "J_sc", "J_t")
+
+
+def _objective_time_call(ctx, N, values, mask, x, params, coeff_times, grid, collision, constraints, state, parts,
+                         constraint_values, maxima, free, coeffs, asynchronous, threads):
+    """Shared body of Context.objective_time_batch (ctx given) and host_objective_time_batch (ctx None)."""
+    lib = nat.load()
+    dev = ctx is not None and _is_torch(x) and x.is_cuda
+    B, V, h, D = values.shape
+    K = V - 1
+    assert h == N // 2 and tuple(mask.shape) == (B, V) and x.shape[0] == B and len(x.shape) == 2
+    assert coeff_times is None or tuple(coeff_times.shape) == (B, K)
+    stride = int(x.shape[1])
+    p = params.native()
+    sp = constraints.native() if constraints is not None else None
+    C = max(int(sp.n_constraints), 1) if sp is not None else 1
+    assert sp is not None or not (constraint_values or maxima), "constraint_values / maxima need constraints"
+    have = {"J_d": p.objective == nat.MTG_OBJECTIVE_TIME_AND_CONSTRAINTS,
+            "J_c": p.objective == nat.MTG_OBJECTIVE_TIME and p.w_c > 0.0,
+            "J_sc": bool(p.use_soft_constraints) or constraint_values or maxima, "J_t": True}
+    if dev:
+        import torch
+        kw = dict(device=x.device)
+        assert grid is None or (_is_torch(grid.distance) and grid.distance.is_cuda), \
+            "device call: grid.distance must be a CUDA tensor"
+        assert x.is_contiguous() and values.is_contiguous() and mask.is_contiguous()
+        assert coeff_times is None or coeff_times.is_contiguous()
+
+        def new(shape, dtype="f8"):
+            return torch.zeros(shape, dtype={"f8": torch.float64, "u1": torch.uint8, "i4": torch.int32}[dtype], **kw)
+        out_maxima = new((B, C, 3)) if maxima else None
+        flags = nat.MTG_FLAG_DEVICE_PTRS | (nat.MTG_FLAG_ASYNC if asynchronous else 0)
+        ctx.set_stream(torch.cuda.current_stream(x.device).cuda_stream)
+    else:
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        coeff_times = np.ascontiguousarray(coeff_times, dtype=np.float64) if coeff_times is not None else None
+        if state is not None:
+            assert state.dtype == OBJECTIVE_STATE_DTYPE and state.flags.c_contiguous and state.shape == (B,)
+
+        def new(shape, dtype="f8"):
+            return np.zeros(shape, dtype={"f8": np.float64, "u1": np.uint8, "i4": np.int32}[dtype])
+        out_maxima = np.zeros((B, C), dtype=EXTREMUM_DTYPE) if maxima else None
+        flags = 0
+        if ctx is not None:
+            ctx.reset_stream()
+    out = {"cost": new((B,)), "grad": None, "weighted_costs": new((B, 4)), "collision": new((B,), "u1"),
+           "status": new((B,), "i4"), "state": state,
+           "constraint_values": new((B, C)) if constraint_values else None, "maxima": out_maxima,
+           "free": new((B, D, V * h)) if free else None, "coeffs": new((B, K, D, N)) if coeffs else None}
+    for k in OBJECTIVE_PARTS:
+        out[k] = new((B,)) if parts and have.get(k) else None
+    pp = nat.ObjectiveParts(*[_addr(out[k]) for k in OBJECTIVE_PARTS])
+    g, keep = grid.native() if grid is not None else (None, None)
+    cp = collision.native() if collision is not None else None
+    tail = (_addr(values), _addr(mask), _addr(x), stride, ctypes.byref(p), _addr(coeff_times),
+            ctypes.byref(g) if g is not None else None, ctypes.byref(cp) if cp is not None else None,
+            ctypes.byref(sp) if sp is not None else None, _addr(out["cost"]), _addr(out["weighted_costs"]),
+            _addr(out["collision"]), _addr(out["constraint_values"]), _addr(out["maxima"]), _addr(out["free"]),
+            _addr(out["coeffs"]), _addr(state), ctypes.byref(pp) if parts else None, _addr(out["status"]))
+    if ctx is not None:
+        nat.check(lib.mtg_objective_time_batch(ctx.handle, N, D, K, B, *tail, flags), ctx.handle)
+    else:
+        nat.check(lib.mtg_host_objective_time_batch(N, D, K, B, *tail, threads))
+    del keep
+    return out
+
+
+def host_objective_time_batch(N, values, mask, x, params, coeff_times=None, grid=None, collision=None,
+                              constraints=None, state=None, parts=False, constraint_values=False, maxima=False,
+                              free=False, coeffs=False, threads=1):
+    """The library's host path of Context.objective_time_batch (mtg_host_objective_time_batch), no GPU: same
+    arguments (numpy arrays) and outputs."""
+    return _objective_time_call(None, N, values, mask, x, params, coeff_times, grid, collision, constraints, state,
+                                parts, constraint_values, maxima, free, coeffs, False, threads)
+
+
+def host_objective_time_bounds_batch(N, D, K, mask, x, objective, initial_stepsize_rel=0.1):
+    """Bounds and initial step of the two set-ups (mtg_host_objective_time_bounds_batch, restated literally):
+    objective 3: step = rel * t, lower 0.1, upper 2 t; objective 4: step = rel * |x|, bounds -+ 2 |x|, then
+    lower 0.1 for the K times.  mask [B][V], x [B][x_stride] in objective_time_batch's layout.  Returns
+    (lower, upper, initial_step), each [B][x_stride] with +0.0 past a row's length."""
+    mask = np.ascontiguousarray(mask, dtype=np.uint8)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    B, stride = x.shape
+    assert mask.shape == (B, K + 1)
+    lo, up, step = np.zeros((B, stride)), np.zeros((B, stride)), np.zeros((B, stride))
+    nat.check(nat.load().mtg_host_objective_time_bounds_batch(N, D, K, B, _addr(mask), int(objective), _addr(x), stride,
+                                                              float(initial_stepsize_rel), _addr(lo), _addr(up),
+                                                              _addr(step)))
     return lo, up, step
 
 
