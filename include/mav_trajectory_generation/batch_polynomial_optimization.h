@@ -266,6 +266,17 @@ class BatchPolynomialOptimization {
                                    offsets, out, sampling_times, flags),
           ctx_, "mtg_evaluate_range_batch");
   }
+  // Trajectory::evaluate of every trajectory at its own query times (mtg_evaluate_at_batch): the time of
+  // trajectory b's query m is t_query[b * t_stride + m] (t_stride 0: one row of M times for the whole
+  // batch); out [B][M][n_derivatives][D] holds orders derivative_begin .. derivative_begin +
+  // n_derivatives - 1, in_range [B][M] whether the time lies inside the trajectory.
+  void evaluateAt(int64_t batch, const double* coeffs, const double* times, const double* t_query, int64_t t_stride,
+                  int64_t M, int derivative_begin, int n_derivatives, double* out, uint8_t* in_range = nullptr,
+                  int32_t* status = nullptr, unsigned flags = 0) {
+    check(mtg_evaluate_at_batch(ctx_, N, D_, K_, batch, coeffs, times, t_query, t_stride, M, derivative_begin,
+                                n_derivatives, out, in_range, status, flags),
+          ctx_, "mtg_evaluate_at_batch");
+  }
 
  private:
   int D_, K_, r_;
@@ -382,6 +393,26 @@ inline void objectiveTime(int D, int K, int64_t batch, const double* values, con
                                         constraints, cost, weighted_costs, is_collision, constraint_values, maxima, free,
                                         coeffs, state, parts, status, 1),
           nullptr, "mtg_host_objective_time_batch");
+  }
+}
+
+// Trajectory::evaluate for trajectories of N coefficients, K segments and D dimensions at their own
+// query times (mtg_evaluate_at_batch), without a BatchPolynomialOptimization object: on the library's
+// host path (mtg_host_evaluate_at_batch) unless the execution policy is kDevice, as collisionCost.
+// The same bits as Trajectory::evaluate called in a loop.  Host pointers.
+template <int N>
+inline void evaluateAt(int D, int K, int64_t batch, const double* coeffs, const double* times, const double* t_query,
+                       int64_t t_stride, int64_t M, int derivative_begin, int n_derivatives, double* out,
+                       uint8_t* in_range = nullptr, int32_t* status = nullptr) {
+  if (singleOnDevice()) {
+    mtg_ctx* ctx = defaultContext();
+    check(mtg_evaluate_at_batch(ctx, N, D, K, batch, coeffs, times, t_query, t_stride, M, derivative_begin,
+                                n_derivatives, out, in_range, status, 0),
+          ctx, "mtg_evaluate_at_batch");
+  } else {
+    check(mtg_host_evaluate_at_batch(N, D, K, batch, coeffs, times, t_query, t_stride, M, derivative_begin,
+                                     n_derivatives, out, in_range, status, 1),
+          nullptr, "mtg_host_evaluate_at_batch");
   }
 }
 

@@ -50,7 +50,9 @@ extern "C" {
                                3: + mtg_collision_time_gradient_batch, mtg_host_collision_time_gradient_batch
                                4: + mtg_objective_batch, mtg_host_objective_batch, mtg_host_objective_bounds_batch
                                5: + mtg_objective_time_batch, mtg_host_objective_time_batch,
-                                    mtg_host_objective_time_bounds_batch */
+                                    mtg_host_objective_time_bounds_batch
+                               5, additive: + mtg_evaluate_at_batch, mtg_host_evaluate_at_batch,
+                                    mtg_evaluate_at_path */
 
 /* Call-level return codes. */
 #define MTG_OK 0
@@ -218,6 +220,50 @@ int mtg_evaluate_range_batch_full(mtg_ctx* ctx, int N, int D, int K, int64_t bat
                                   const double* times, double t_start, double t_end, double dt, int derivative,
                                   int64_t* counts, int64_t* offsets, int64_t* total, double* out,
                                   double* sample_times, int64_t capacity, unsigned flags);
+
+/* Batched Trajectory::evaluate (src/trajectory.cpp:41-66) at caller-given query times, several
+ * derivative orders from one pass over the coefficients (Polynomial::evaluate(t, VectorXd*),
+ * polynomial.h:120-134, each order as polynomial.h:138-151).  The output shape is known in advance:
+ * no counts, no offsets, no prefix sum.
+ *   coeffs [B][K][D][N] (as the solve writes them), times [B][K]
+ *   t_query: the time of trajectory b's query m is t_query[b * t_stride + m]; t_stride == 0 is one
+ *            row of M times shared by the whole batch, otherwise t_stride >= M
+ *   out [B][M][n_derivatives][D]: orders derivative_begin .. derivative_begin + n_derivatives - 1
+ *   in_range_out [B][M] (nullable), status [B] (nullable: MTG_TRAJ_BAD_TIME)
+ * Per trajectory b and query time t:
+ *   segment    acc = 0; for i = 0 .. K-1: acc = fl(acc + T_i), stop at the first i with acc > t
+ *              (sequential FP64 adds, trajectory.cpp:42-57).
+ *   beyond     t > acc after the loop (+inf included): the row is all +0.0 and in_range = 0
+ *              (trajectory.cpp:58-61; no message is printed).
+ *   the end    the loop ran out and t > acc is false (t equals the accumulated total): the reference
+ *              indexes one past the last segment; the last segment is used (i = K-1), in_range = 1.
+ *   NaN        a NaN t gives a NaN row and in_range = 0.
+ *   otherwise  in_range = 1, also for t < 0 (-inf included): the first segment is evaluated at a
+ *              negative local time, as the reference does.
+ *   local time tl = fl(t - fl(acc - T_i)), acc the value after adding T_i (trajectory.cpp:63-65);
+ *              not simplified.
+ *   value      order k >= N: +0.0.  Otherwise r = fl(base(k, N-1) c[N-1]); for j = N-2 .. k:
+ *              r = fl(r tl), r = fl(r + fl(base(k, j) c[j])), base(k, j) = j!/(j-k)!
+ *              (polynomial.h:138-151).  Multiply and add are separate roundings: no FMA, on the
+ *              device or on the host, so both give the reference's bits.
+ *   bad times  a trajectory with some T_i <= 0 or not finite: MTG_TRAJ_BAD_TIME, all its rows NaN
+ *              and its in_range 0.
+ * Errors: MTG_ERR_UNSUPPORTED_N; MTG_ERR_SIZE_MISMATCH (K < 1, D < 1, batch < 0, M < 0);
+ * MTG_ERR_BAD_DERIVATIVE (derivative_begin < 0, n_derivatives outside 1..N);
+ * MTG_ERR_INVALID_ARGUMENT (NULL ctx; t_stride < 0 or 0 < t_stride < M; coeffs, times, t_query or
+ * out NULL with batch * M > 0); MTG_ERR_TOO_LARGE (a 64-thread block's rows exceed LDS:
+ * n_derivatives * D > 128).  batch == 0 or M == 0: MTG_OK, nothing written.
+ * Two kernels, picked from the shape alone (mtg_evaluate_at_path): a query's bits
+ * depend neither on the kernel nor on the call it is part of. */
+#define MTG_EVALUATE_AT_LANE 1         /* a lane per (trajectory, query): few queries per trajectory */
+#define MTG_EVALUATE_AT_STAGED 2       /* a block per (trajectory, chunk of queries), coefficients in LDS */
+int mtg_evaluate_at_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* coeffs,
+                          const double* times, const double* t_query, int64_t t_stride, int64_t M,
+                          int derivative_begin, int n_derivatives, double* out, uint8_t* in_range_out,
+                          int32_t* status, unsigned flags);
+/* The kernel (MTG_EVALUATE_AT_*) mtg_evaluate_at_batch runs for this shape -- staged iff
+ * M >= max(32, K) and the staged block fits LDS -- or a negative MTG_ERR_*.  No device work. */
+int mtg_evaluate_at_path(int N, int D, int K, int64_t M, int n_derivatives);
 
 /* Batched segment-time sweep (the nonlinear time-allocation objective,
  * polynomial_optimization_nonlinear_impl.h:765-832 via updateSegmentTimes +
@@ -816,6 +862,15 @@ int mtg_host_default_threads(void);
 int mtg_host_min_max_magnitude_batch(int N, int D, int K, int64_t batch, const double* coeffs, const double* times,
                                      int derivative, uint32_t dimension_mask, mtg_extremum* minimum,
                                      mtg_extremum* maximum, int threads);
+
+/* Host (CPU) path of mtg_evaluate_at_batch, no context and no GPU needed: the definition there
+ * followed literally in scalar code (the linear scan of trajectory.cpp:42-57, not a binary search),
+ * threaded over trajectories.  The same bits as the kernels; the C++ drop-in's evaluateAt<N> uses it
+ * unless ExecutionPolicy::kDevice.  All host pointers; the argument errors of mtg_evaluate_at_batch
+ * (no MTG_ERR_TOO_LARGE); threads <= 0: mtg_host_default_threads(). */
+int mtg_host_evaluate_at_batch(int N, int D, int K, int64_t batch, const double* coeffs, const double* times,
+                               const double* t_query, int64_t t_stride, int64_t M, int derivative_begin,
+                               int n_derivatives, double* out, uint8_t* in_range_out, int32_t* status, int threads);
 
 /* ---- Host utilities (no GPU): the reference's synthetic-input generators,
  * bit-exact with libstdc++ <random>, packed straight into the ABI layout.

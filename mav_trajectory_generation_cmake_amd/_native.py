@@ -45,6 +45,9 @@ KERNEL_NAMES = {MTG_KERNEL_COLUMN: "solve_reg_kernel",
                 MTG_KERNEL_GENERAL: "solve_fused_kernel", MTG_KERNEL_SPLIT: "assemble+block_cholesky",
                 MTG_KERNEL_DL: "solve_dl_kernel", MTG_KERNEL_DLX: "solve_dlx_kernel"}
 
+MTG_EVALUATE_AT_LANE = 1
+MTG_EVALUATE_AT_STAGED = 2
+
 MTG_OBJECTIVE_FREE_CONSTRAINTS = 0
 MTG_OBJECTIVE_FREE_CONSTRAINTS_AND_COLLISION = 1
 MTG_OBJECTIVE_FREE_CONSTRAINTS_AND_COLLISION_AND_TIME = 2
@@ -131,6 +134,13 @@ _SIGNATURES = {
                                                      ctypes.c_int64, _c_dp, _c_dp, ctypes.c_double, ctypes.c_double,
                                                      ctypes.c_double, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
                                                      ctypes.c_int64, ctypes.c_uint]),
+    "mtg_evaluate_at_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                             _c_dp, _c_dp, _c_dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                             ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_uint]),
+    "mtg_evaluate_at_path": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
+    "mtg_host_evaluate_at_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _c_dp,
+                                                  _c_dp, _c_dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                                  ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mtg_time_sweep_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_int64, _c_dp, _c_dp, _c_dp, ctypes.c_int,
                                             _c_dp, _c_dp, _c_dp, ctypes.c_uint]),
@@ -311,6 +321,15 @@ def solve_kernel(N, D, K, r, flags=0, B=None):
     if code < 0:
         raise MTGError(code, status_string(code))
     return KERNEL_NAMES[code]
+
+
+def evaluate_at_path(N, D, K, M, n_derivatives=1):
+    """The kernel mtg_evaluate_at_batch runs for this shape (mtg_evaluate_at_path): MTG_EVALUATE_AT_LANE or
+    MTG_EVALUATE_AT_STAGED.  Depends on the shape only."""
+    code = load().mtg_evaluate_at_path(N, D, K, M, n_derivatives)
+    if code < 0:
+        raise MTGError(code, status_string(code))
+    return code
 
 
 def device_count():

@@ -1645,6 +1645,54 @@ int mtg_min_max_magnitude_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch
   return st.finish();
 }
 
+int mtg_evaluate_at_path(int N, int D, int K, int64_t M, int n_derivatives) {
+  if (int rc = check_order(nullptr, N)) return rc;
+  if (int rc = check_dims(nullptr, D, K, M)) return rc;
+  if (n_derivatives < 1 || n_derivatives > N) return MTG_ERR_BAD_DERIVATIVE;
+  mtg::EvalAtPlan plan;
+  return mtg::evaluate_at_plan(N, D, K, M, n_derivatives, &plan) ? plan.path : MTG_ERR_TOO_LARGE;
+}
+
+int mtg_evaluate_at_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* coeffs,
+                          const double* times, const double* t_query, int64_t t_stride, int64_t M,
+                          int derivative_begin, int n_derivatives, double* out, uint8_t* in_range_out,
+                          int32_t* status, unsigned flags) {
+  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
+  if (int rc = check_order(ctx, N)) return rc;
+  if (int rc = check_dims(ctx, D, K, batch)) return rc;
+  if (M < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need M >= 0");
+  if (derivative_begin < 0 || n_derivatives < 1 || n_derivatives > N)
+    return set_error(ctx, MTG_ERR_BAD_DERIVATIVE, "need derivative_begin >= 0 and n_derivatives in [1, N]");
+  if (t_stride < 0 || (t_stride > 0 && t_stride < M))
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "t_stride must be 0 (shared query times) or >= M");
+  mtg::EvalAtPlan plan;
+  if (!mtg::evaluate_at_plan(N, D, K, M, n_derivatives, &plan))
+    return set_error(ctx, MTG_ERR_TOO_LARGE, "a block's rows exceed LDS (n_derivatives * D > 128)");
+  if (batch == 0 || M == 0) return MTG_OK;
+  if (!coeffs || !times || !t_query || !out)
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "coeffs, times, t_query and out are required");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t nB = (size_t)batch, nM = (size_t)M;
+  const double *d_coef, *d_times, *d_tq;
+  double* d_out;
+  uint8_t* d_in;
+  int32_t* d_status;
+  Staged st(ctx, flags);
+  st.in(&d_coef, coeffs, sizeof(double) * nB * K * D * N);
+  st.in(&d_times, times, sizeof(double) * nB * K);
+  st.in(&d_tq, t_query, sizeof(double) * (t_stride ? (nB - 1) * (size_t)t_stride + nM : nM));
+  st.out(&d_out, out, sizeof(double) * nB * nM * n_derivatives * D);
+  st.out(&d_in, in_range_out, nB * nM);
+  st.out(&d_status, status, sizeof(int32_t) * nB);
+  if (int rc = st.upload()) return rc;
+  MTG_HIP_TRY(ctx, time_begin(ctx));
+  MTG_HIP_TRY(ctx, mtg::launch_evaluate_at(N, D, K, batch, d_coef, d_times, d_tq, t_stride, M, derivative_begin,
+                                           n_derivatives, d_out, d_in, d_status, ctx->stream));
+  MTG_HIP_TRY(ctx, time_end(ctx));
+  return st.finish();
+}
+
 int mtg_evaluate_range_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch,
                              const double* coeffs, const double* times, double t_start,
                              double t_end, double dt, int derivative, int64_t* counts,

@@ -204,6 +204,18 @@ hipError_t launch_min_max_magnitude(int N, const double* coeffs, const double* t
                                     int derivative, unsigned dims, mtg_extremum* mn, mtg_extremum* mx,
                                     hipStream_t stream);
 
+// Trajectory::evaluate at caller-given times (mtg_evaluate_at.hip).  evaluate_at_plan is the one rule
+// that picks the mapping (path: MTG_EVALUATE_AT_LANE or MTG_EVALUATE_AT_STAGED) and the block's
+// threads and LDS bytes from the shape alone; false: a block's rows do not fit in LDS.
+struct EvalAtPlan {
+  int path, threads;
+  size_t lds;
+};
+bool evaluate_at_plan(int N, int D, int K, int64_t M, int n_derivatives, EvalAtPlan* plan);
+hipError_t launch_evaluate_at(int N, int D, int K, int64_t B, const double* coeffs, const double* times,
+                              const double* t_query, int64_t t_stride, int64_t M, int derivative_begin,
+                              int n_derivatives, double* out, uint8_t* in_range, int32_t* status, hipStream_t stream);
+
 // evaluateRange
 hipError_t launch_eval_count(int N, int D, int K, int64_t B, const double* times, double t_start,
                              double t_end, double dt, int64_t* counts, hipStream_t stream);

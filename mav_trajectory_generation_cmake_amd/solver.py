@@ -592,6 +592,80 @@ class Context:
         return out[:n], (st[:n] if want_times else None), counts, offsets
 
 
+    # --------------------------------------------------------- evaluate
+    def evaluate_at_batch(self, coeffs, times, t_query, derivative_begin=0, n_derivatives=1, want_in_range=True,
+                          asynchronous=False):
+        """Trajectory::evaluate of every trajectory at caller-given times (include/mtg.h
+        mtg_evaluate_at_batch): coeffs [B][K][D][N], times [B][K]; t_query [M] (one row of times shared by
+        the batch) or [B][M], also as a view whose rows are contiguous and at least M elements apart.
+        numpy arrays or torch CUDA tensors (then the launch goes to torch's current stream and
+        asynchronous=True does not wait for it).  Returns (out [B][M][n_derivatives][D] with the orders
+        derivative_begin .. derivative_begin + n_derivatives - 1, in_range [B][M] uint8 or None,
+        status [B] int32)."""
+        dev = _is_torch(coeffs) and coeffs.is_cuda
+        B, K, D, N = coeffs.shape
+        assert tuple(times.shape) == (B, K)
+        if dev:
+            import torch
+            kw = dict(device=coeffs.device)
+            coeffs, times = coeffs.contiguous(), times.contiguous()
+            t_query, t_stride, M = _query_rows(t_query, B, lambda a: a.stride(), lambda a: a.contiguous())
+            out = torch.empty((B, M, n_derivatives, D), dtype=torch.float64, **kw)
+            in_range = torch.empty((B, M), dtype=torch.uint8, **kw) if want_in_range else None
+            status = torch.empty(B, dtype=torch.int32, **kw)
+            flags = nat.MTG_FLAG_DEVICE_PTRS | (nat.MTG_FLAG_ASYNC if asynchronous else 0)
+            self.set_stream(torch.cuda.current_stream(coeffs.device).cuda_stream)
+        else:
+            coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+            times = np.ascontiguousarray(times, dtype=np.float64)
+            t_query, t_stride, M = _query_rows_numpy(t_query, B)
+            out = np.empty((B, M, n_derivatives, D))
+            in_range = np.empty((B, M), np.uint8) if want_in_range else None
+            status = np.empty(B, np.int32)
+            flags = 0
+            self.reset_stream()
+        nat.check(self._lib.mtg_evaluate_at_batch(self.handle, N, D, K, B, _addr(coeffs), _addr(times), _addr(t_query),
+                                                  t_stride, M, int(derivative_begin), int(n_derivatives), _addr(out),
+                                                  _addr(in_range), _addr(status), flags), self.handle)
+        return out, in_range, status
+
+
+def _query_rows(t_query, B, strides, contiguous):
+    """(array, t_stride, M) of evaluate_at's query times: [M] is shared (stride 0); [B][M] keeps its row
+    stride when its rows are contiguous and at least M elements apart, else it is made contiguous."""
+    if t_query.ndim == 1:
+        return contiguous(t_query), 0, int(t_query.shape[0])
+    assert t_query.ndim == 2 and t_query.shape[0] == B, "t_query must be [M] or [B][M]"
+    M = int(t_query.shape[1])
+    s = strides(t_query)
+    if M > 0 and B > 0 and not (s[1] == 1 and (s[0] >= M or B == 1)):
+        t_query = contiguous(t_query)
+        s = (M, 1)
+    return t_query, (max(int(s[0]), M) if M > 0 else 0), M
+
+
+def _query_rows_numpy(t_query, B):
+    t_query = np.asarray(t_query, dtype=np.float64)
+    return _query_rows(t_query, B, lambda a: tuple(x // a.itemsize for x in a.strides), np.ascontiguousarray)
+
+
+def host_evaluate_at_batch(coeffs, times, t_query, derivative_begin=0, n_derivatives=1, want_in_range=True, threads=0):
+    """Context.evaluate_at_batch on the library's host path (mtg_host_evaluate_at_batch): no GPU; the same
+    bits as the kernels.  numpy arrays; threads <= 0: mtg_host_default_threads()."""
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    B, K, D, N = coeffs.shape
+    assert tuple(times.shape) == (B, K)
+    t_query, t_stride, M = _query_rows_numpy(t_query, B)
+    out = np.empty((B, M, n_derivatives, D))
+    in_range = np.empty((B, M), np.uint8) if want_in_range else None
+    status = np.empty(B, np.int32)
+    nat.check(nat.load().mtg_host_evaluate_at_batch(N, D, K, B, _addr(coeffs), _addr(times), _addr(t_query), t_stride,
+                                                    M, int(derivative_begin), int(n_derivatives), _addr(out),
+                                                    _addr(in_range), _addr(status), int(threads)))
+    return out, in_range, status
+
+
 def evaluate_range_capacity(times, t_start, t_end, dt):
     """A safe sample capacity for evaluateRange over a batch (mtg_evaluate_range_batch_full): per
     trajectory the clock samples while the accumulated time (>= 0) is below t_end and the sample is
