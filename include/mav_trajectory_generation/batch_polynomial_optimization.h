@@ -6,6 +6,8 @@
 // Arrays are in the C ABI layout (include/mtg.h): values [B][K+1][N/2][D], mask [B][K+1] (bit k:
 // derivative k fixed), times [B][K], coeffs [B][K][D][N].  Pass MTG_FLAG_DEVICE_PTRS to hand over
 // device pointers (inputs already in HBM); host pointers are staged by the library.
+// solveRagged takes problems of different segment counts in one call (CSR arrays, include/mtg.h
+// mtg_solve_linear_ragged_batch): the one entry here that is not tied to the object's K.
 //
 // Several devices: construct with a device list (e.g. allDevices()).  A host-array solve() is then
 // one mtg_solve_linear_batch_multi call: contiguous shards of the batch, one host thread and one
@@ -122,6 +124,48 @@ class BatchPolynomialOptimization {
     if (status) status->assign((size_t)B, 0);
     solve(B, vals.data(), mask.data(), t.data(), coeffs->data(), cost ? cost->data() : nullptr,
           status ? status->data() : nullptr);
+  }
+  // The same for problems of different segment counts (mtg_solve_linear_ragged_batch): seg_count [batch]
+  // is a host array also with MTG_FLAG_DEVICE_PTRS, the other arrays are the CSR arrays of include/mtg.h
+  // (trajectory b at vertex offset sum_{j<b} (K_j + 1) and segment offset sum_{j<b} K_j).  The object's
+  // `segments` is not used; runs on the first device.
+  void solveRagged(int64_t batch, const int32_t* seg_count, const double* values, const uint8_t* mask,
+                   const double* times, double* coeffs, double* cost = nullptr, int32_t* status = nullptr,
+                   unsigned flags = 0, double* free_out = nullptr, int32_t* n_free = nullptr) {
+    check(mtg_solve_linear_ragged_batch(ctx_, N, D_, r_, batch, seg_count, values, mask, times, coeffs, free_out,
+                                        n_free, cost, status, flags),
+          ctx_, "mtg_solve_linear_ragged_batch");
+  }
+  // Problems given as Vertex lists of any length >= 2 each, with their segment times.  coeffs receives
+  // [sum K][D][N]; problem b's segments start at (*segment_offsets)[b] (B + 1 entries, the last the total).
+  void solveRagged(const std::vector<Vertex::Vector>& problems, const std::vector<std::vector<double>>& times,
+                   std::vector<double>* coeffs, std::vector<int64_t>* segment_offsets = nullptr,
+                   std::vector<double>* cost = nullptr, std::vector<int32_t>* status = nullptr) {
+    const int64_t B = (int64_t)problems.size();
+    const int h = N / 2;
+    if ((int64_t)times.size() != B) fail(MTG_ERR_SIZE_MISMATCH, "one segment-time vector per problem");
+    std::vector<int32_t> seg((size_t)B);
+    std::vector<int64_t> so((size_t)B + 1, 0);
+    for (int64_t b = 0; b < B; ++b) {
+      if (problems[b].size() < 2 || times[b].size() + 1 != problems[b].size())
+        fail(MTG_ERR_SIZE_MISMATCH, "every problem needs V >= 2 vertices and V - 1 segment times");
+      seg[b] = (int32_t)times[b].size();
+      so[b + 1] = so[b] + seg[b];
+    }
+    const size_t totS = (size_t)so[B], totV = totS + (size_t)B;
+    std::vector<double> vals(totV * h * D_), t(totS);
+    std::vector<uint8_t> mask(totV);
+    for (int64_t b = 0; b < B; ++b) {
+      const size_t v0 = (size_t)(so[b] + b);
+      packVertices(problems[b], N, D_, vals.data() + v0 * h * D_, mask.data() + v0);
+      for (int i = 0; i < seg[b]; ++i) t[(size_t)so[b] + i] = times[b][i];
+    }
+    check_notnull(coeffs, "coeffs")->assign(totS * D_ * N, 0.0);
+    if (cost) cost->assign((size_t)B, 0.0);
+    if (status) status->assign((size_t)B, 0);
+    solveRagged(B, seg.data(), vals.data(), mask.data(), t.data(), coeffs->data(), cost ? cost->data() : nullptr,
+                status ? status->data() : nullptr);
+    if (segment_offsets) *segment_offsets = so;
   }
   // time-allocation sweep: optimal cost at scale[c] * times (mtg_time_sweep_batch)
   void timeSweep(int64_t batch, const double* values, const uint8_t* mask, const double* times, int n_candidates,

@@ -52,7 +52,9 @@ extern "C" {
                                5: + mtg_objective_time_batch, mtg_host_objective_time_batch,
                                     mtg_host_objective_time_bounds_batch
                                5, additive: + mtg_evaluate_at_batch, mtg_host_evaluate_at_batch,
-                                    mtg_evaluate_at_path */
+                                    mtg_evaluate_at_path
+                               5, additive: + mtg_solve_linear_ragged_batch, mtg_host_solve_linear_ragged_batch,
+                                    mtg_solve_ragged_plan */
 
 /* Call-level return codes. */
 #define MTG_OK 0
@@ -162,6 +164,58 @@ int mtg_solve_linear_batch(mtg_ctx* ctx, int N, int D, int K, int derivative_to_
                            const double* times, double* coeffs, double* free_out,
                            int32_t* n_free_out, double* cost_out, int32_t* status,
                            unsigned flags);
+
+/* mtg_solve_linear_batch for a batch whose trajectories have different segment counts (ragged K):
+ * PolynomialOptimization<N> takes any number of vertices per instance, and a planner's candidate
+ * paths have a different waypoint count each.  One call, no bucketing by the caller.
+ *
+ * Layout (CSR, no padding).  K_b = seg_count[b], V_b = K_b + 1; vo[b] = sum_{j<b} V_j and
+ * so[b] = sum_{j<b} K_j, both 64-bit.  Trajectory b owns
+ *   values     [vo[b] .. vo[b] + V_b][h][D]
+ *   fixed_mask [vo[b] .. vo[b] + V_b]
+ *   times      [so[b] .. so[b] + K_b]
+ *   coeffs     [so[b] .. so[b] + K_b][D][N]
+ *   free_out   the block [D][V_b h] at double offset D h vo[b]; entries >= n_free are +0.0
+ *   n_free_out[b], cost_out[b], status[b]
+ * Each block is exactly what mtg_solve_linear_batch reads or writes for one trajectory of K_b
+ * segments, so a run of consecutive trajectories with equal K is a valid uniform array for every
+ * uniform-K entry point.  The nullable outputs are those of the uniform call.
+ * seg_count [B] is shape metadata, like K in the uniform call: a HOST array also with
+ * MTG_FLAG_DEVICE_PTRS, read during the call and not kept.
+ *
+ * Semantics: for every b, every output byte equals what
+ * mtg_solve_linear_batch(ctx, N, D, K_b, r, 1, ...that trajectory's blocks..., flags) writes, the
+ * status bits and whatever the coefficients hold under an error bit included.  flags pass to every
+ * group unchanged (MTG_FLAG_GENERAL_KERNEL, _DL_KERNEL, _COLUMN_KERNEL, _SPLIT_KERNELS; _DEVICE_PTRS
+ * and _ASYNC with their usual meaning); the kernel for K_b is mtg_solve_kernel(N, D, K_b, r, flags).
+ *
+ * The plan (host code, mtg_solve_ragged_plan reports it).  A group is all trajectories with one K.
+ * A group whose members are consecutive in the batch (one run) is solved in place: the uniform
+ * launcher runs on slices of the caller's arrays and nothing is copied.  Every other group is
+ * gathered: one kernel copies its inputs into packed uniform arrays owned by the context, the
+ * uniform launcher runs there, and one kernel copies the outputs to their CSR positions.  Groups are
+ * launched in ascending K on the context's stream with no host synchronisation in between.  A caller
+ * who sorts the batch by K gets every group in place (zero copies).  In-place slices are 8-byte
+ * aligned for the doubles and byte aligned for the mask whatever the arrays' own alignment; coeffs
+ * slices keep the alignment of coeffs modulo 16 (K D N is even).  The solve kernels need no more
+ * (DESIGN.md 3.14).
+ * Host-pointer calls stage the CSR arrays whole and run the same path (no chunked pipeline).
+ * mtg_last_kernel_ms spans the call's first to its last kernel.  Two MTG_FLAG_ASYNC calls on one
+ * context may follow each other without a synchronisation between them.
+ *
+ * Errors, all before any device work: those of the uniform call on N, D, r and batch;
+ * MTG_ERR_INVALID_ARGUMENT for seg_count == NULL with batch > 0; MTG_ERR_SIZE_MISMATCH for any
+ * seg_count[b] < 1; the code of mtg_solve_kernel if it rejects some K that is present
+ * (MTG_ERR_TOO_LARGE).  batch == 0: MTG_OK. */
+int mtg_solve_linear_ragged_batch(mtg_ctx* ctx, int N, int D, int derivative_to_optimize, int64_t batch,
+                                  const int32_t* seg_count, const double* values, const uint8_t* fixed_mask,
+                                  const double* times, double* coeffs, double* free_out, int32_t* n_free_out,
+                                  double* cost_out, int32_t* status, unsigned flags);
+/* The plan of that call for these segment counts, with its call-level errors: *n_groups distinct K,
+ * *n_in_place trajectories in groups solved in place (== batch for a batch sorted by K),
+ * *total_segments = sum K_b (any pointer may be NULL).  No context, no device work. */
+int mtg_solve_ragged_plan(int N, int D, int derivative_to_optimize, int64_t batch, const int32_t* seg_count,
+                          unsigned flags, int64_t* n_groups, int64_t* n_in_place, int64_t* total_segments);
 
 /* Contiguous shard `shard` (0 <= shard < n_shards) of a batch of `batch` independent problems:
  * [*begin, *end) = [g ceil(B/G), min(B, (g+1) ceil(B/G))).  The partition that
@@ -848,6 +902,16 @@ int mtg_host_solve_linear_batch(int N, int D, int K, int derivative_to_optimize,
                                 const double* values, const uint8_t* fixed_mask, const double* times,
                                 double* coeffs, double* free_out, int32_t* n_free_out, double* cost_out,
                                 int32_t* status, int threads);
+
+/* Host (CPU) path of mtg_solve_linear_ragged_batch, no context and no GPU needed: the same CSR
+ * arrays (all host pointers) and the same plan offsets; every trajectory is solved on its own blocks
+ * by the code behind mtg_host_solve_linear_batch, so its outputs are the bytes that call writes for
+ * a batch of one.  Threaded over trajectories; threads <= 0: mtg_host_default_threads().  The
+ * call-level errors of the device call except MTG_ERR_TOO_LARGE (the host solver has no size limit). */
+int mtg_host_solve_linear_ragged_batch(int N, int D, int derivative_to_optimize, int64_t batch,
+                                       const int32_t* seg_count, const double* values, const uint8_t* fixed_mask,
+                                       const double* times, double* coeffs, double* free_out, int32_t* n_free_out,
+                                       double* cost_out, int32_t* status, int threads);
 
 /* The worker count the host paths (mtg_host_*) use when called with threads <= 0: the CPUs this
  * process may run on -- its affinity mask, capped by the cgroup CPU quota -- not every CPU of the

@@ -21,6 +21,7 @@
 
 #include "mtg.h"
 #include "mtg_internal.h"
+#include "mtg_ragged_plan.h"
 
 // A persistent host thread of a context that runs one job at a time for the caller (the pipelined
 // solve's D2H issuer): created on first use and kept, instead of a std::thread per call (~50-100 us of
@@ -107,6 +108,21 @@ struct mtg_ctx {
   hipStream_t pipe_h2d = nullptr, pipe_d2h = nullptr;
   hipEvent_t pipe_start = nullptr;
   CtxWorker d2h_worker;
+  // Ragged solves (run_solve_ragged): the device copy of the plan records and the packed arrays of the
+  // gathered groups.  Not ctx->workspace: the DLX and split kernels use that during the same call.
+  void* ragged = nullptr;
+  size_t ragged_bytes = 0;
+  // the records are uploaded from pinned memory the context owns (an asynchronous copy outlives the
+  // call); two buffers taken in turn, each reused only after the event behind its last upload
+  struct RaggedHost {
+    void* p = nullptr;
+    size_t bytes = 0;
+    hipEvent_t uploaded = nullptr;
+    bool pending = false;
+  } ragged_host[2];
+  int ragged_turn = 0;
+  hipEvent_t ragged_done = nullptr;  // the last ragged call's last kernel (it may have run on another stream)
+  bool ragged_done_pending = false;
 };
 
 namespace mtg {
@@ -770,6 +786,194 @@ int run_solve(mtg_ctx* ctx, int N, int D, int K, int r, int64_t batch, const dou
   return MTG_OK;
 }
 
+// The call-level checks the three ragged entries share, in the order they are reported, and the plan.
+// ctx may be NULL (mtg_solve_ragged_plan has none).  batch == 0 leaves an empty plan.
+int ragged_check_and_plan(mtg_ctx* ctx, int N, int D, int r, int64_t batch, const int32_t* seg_count, unsigned flags,
+                          mtg::RaggedPlan* plan) {
+  int rc = check_order(ctx, N);
+  if (rc != MTG_OK) return rc;
+  if (r < 0 || r > N / 2 - 1)
+    return set_error(ctx, MTG_ERR_BAD_DERIVATIVE, "derivative_to_optimize must be in [0, N/2-1]");
+  if (D < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need D >= 1, batch >= 0");
+  *plan = mtg::RaggedPlan{};
+  plan->vo.assign(1, 0);
+  plan->pvo.assign(1, 0);
+  if (batch == 0) return MTG_OK;
+  if (!seg_count) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "seg_count is required (a host array)");
+  try {
+    rc = mtg::ragged_plan(batch, seg_count, plan);
+  } catch (const std::bad_alloc&) {
+    return set_error(ctx, MTG_ERR_OUT_OF_MEMORY, "ragged plan: out of host memory");
+  }
+  if (rc != MTG_OK) return set_error(ctx, rc, "every seg_count must be >= 1");
+  for (const mtg::RaggedGroup& g : plan->groups) {
+    rc = mtg_solve_kernel(N, D, g.K, r, flags);
+    if (rc < 0) return set_error(ctx, rc, "a segment count of the batch is rejected by mtg_solve_kernel");
+  }
+  return MTG_OK;
+}
+
+// Body of mtg_solve_linear_ragged_batch: the gathered groups' inputs into packed
+// arrays (one kernel), one uniform solve launch per group in ascending K -- in place on slices of the
+// CSR arrays, or on the packed arrays -- and the gathered groups' outputs back (one kernel); all on
+// ctx->stream with no host synchronisation in between.
+int run_solve_ragged(mtg_ctx* ctx, int N, int D, int r, const mtg::RaggedPlan& plan, const double* values,
+                     const uint8_t* mask, const double* times, double* coeffs, double* free_out, int32_t* n_free_out,
+                     double* cost_out, int32_t* status, unsigned flags) {
+  const int h = N / 2;
+  const size_t hD = (size_t)h * D, DN = (size_t)D * N;
+  const int64_t batch = (int64_t)plan.vo.size() - 1;
+  const size_t totV = (size_t)plan.total_vertices(), totS = (size_t)plan.total_segments();
+  const size_t nG = plan.members.size(), gV = (size_t)plan.pvo.back(), gS = gV - nG;
+  MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const double *d_vals, *d_times;
+  const uint8_t* d_mask;
+  double *d_coeffs, *d_free, *d_cost;
+  int32_t *d_nfree, *d_status;
+  const size_t b_free = sizeof(double) * totV * hD;
+  Staged st(ctx, flags);
+  st.in(&d_vals, values, sizeof(double) * totV * hD);
+  st.in(&d_mask, mask, totV);
+  st.in(&d_times, times, sizeof(double) * totS);
+  st.out(&d_coeffs, coeffs, sizeof(double) * totS * DN);
+  st.out(&d_free, free_out, b_free);
+  st.out(&d_nfree, n_free_out, sizeof(int32_t) * (size_t)batch);
+  st.out(&d_cost, cost_out, sizeof(double) * (size_t)batch);
+  st.out(&d_status, status, sizeof(int32_t) * (size_t)batch);
+  // an earlier ragged call may have run on another stream (mtg_set_stream): this call reuses its
+  // packed arrays and record buffer
+  if (ctx->ragged_done_pending) MTG_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ragged_done, 0));
+  if (int rc = st.upload()) return rc;
+
+  // the DLX / split workspace, sized once for the largest group that needs it, before the first
+  // launch: growing it between launches would free memory a queued kernel uses
+  const unsigned ksel = flags & (MTG_FLAG_GENERAL_KERNEL | MTG_FLAG_DL_KERNEL | MTG_FLAG_COLUMN_KERNEL);
+  const bool split = flags & MTG_FLAG_SPLIT_KERNELS;
+  size_t work = 0;
+  for (const mtg::RaggedGroup& g : plan.groups) {
+    if (split) work = std::max(work, mtg::split_workspace_bytes(N, D, g.K, g.count));
+    else if (mtg::solve_kernel(N, D, g.K, ksel, r, g.count) == MTG_KERNEL_DLX)
+      work = std::max(work, mtg::dlx_workspace_bytes(N, D, g.K, g.count));
+  }
+  if (work) MTG_HIP_TRY(ctx, ensure(&ctx->workspace, &ctx->workspace_bytes, std::max<size_t>(work, 256)));
+
+  // the ragged buffer: the records, then the packed arrays of the gathered trajectories (only the
+  // outputs the caller asked for), 256-B aligned each
+  mtg::RaggedCopyArgs ca{};
+  if (nG) {
+    size_t off = 0;
+    const size_t o_recs = off; off = align_up(off + sizeof(mtg::RaggedRec) * nG);
+    const size_t o_vals = off; off = align_up(off + sizeof(double) * gV * hD);
+    const size_t o_mask = off; off = align_up(off + gV);
+    const size_t o_times = off; off = align_up(off + sizeof(double) * gS);
+    const size_t o_coef = off; off = align_up(off + (d_coeffs ? sizeof(double) * gS * DN : 0));
+    const size_t o_free = off; off = align_up(off + (d_free ? sizeof(double) * gV * hD : 0));
+    const size_t o_nfree = off; off = align_up(off + (d_nfree ? sizeof(int32_t) * nG : 0));
+    const size_t o_cost = off; off = align_up(off + (d_cost ? sizeof(double) * nG : 0));
+    const size_t o_status = off; off = align_up(off + (d_status ? sizeof(int32_t) * nG : 0));
+    MTG_HIP_TRY(ctx, ensure(&ctx->ragged, &ctx->ragged_bytes, off));
+    char* base = static_cast<char*>(ctx->ragged);
+    // the records, written into the pinned buffer whose turn it is once its last upload has landed
+    mtg_ctx::RaggedHost& hb = ctx->ragged_host[ctx->ragged_turn];
+    ctx->ragged_turn ^= 1;
+    if (!hb.uploaded) MTG_HIP_TRY(ctx, hipEventCreateWithFlags(&hb.uploaded, hipEventDisableTiming));
+    if (hb.pending) {
+      MTG_HIP_TRY(ctx, hipEventSynchronize(hb.uploaded));
+      hb.pending = false;
+    }
+    const size_t b_recs = sizeof(mtg::RaggedRec) * nG;
+    if (hb.bytes < b_recs) {
+      if (hb.p) MTG_HIP_TRY(ctx, hipHostFree(hb.p));
+      hb.p = nullptr;
+      hb.bytes = 0;
+      const size_t want = std::max<size_t>(b_recs + b_recs / 2, 4096);
+      MTG_HIP_TRY(ctx, hipHostMalloc(&hb.p, want, hipHostMallocDefault));
+      hb.bytes = want;
+    }
+    mtg::RaggedRec* recs = static_cast<mtg::RaggedRec*>(hb.p);
+    for (size_t j = 0; j < nG; ++j) {
+      const int64_t b = plan.members[j];
+      recs[j] = mtg::RaggedRec{plan.vo[(size_t)b], plan.pvo[j], b, (int32_t)(plan.vo[(size_t)b + 1] - plan.vo[(size_t)b] - 1), 0};
+    }
+    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_recs, hb.p, b_recs, hipMemcpyHostToDevice, ctx->stream));
+    MTG_HIP_TRY(ctx, hipEventRecord(hb.uploaded, ctx->stream));
+    hb.pending = true;
+    ca.recs = reinterpret_cast<const mtg::RaggedRec*>(base + o_recs);
+    ca.n = (int64_t)nG;
+    ca.hD = (int)hD;
+    ca.DN = (int)DN;
+    ca.values = d_vals;
+    ca.mask = d_mask;
+    ca.times = d_times;
+    ca.coeffs = d_coeffs;
+    ca.free = d_free;
+    ca.cost = d_cost;
+    ca.n_free = d_nfree;
+    ca.status = d_status;
+    ca.p_values = reinterpret_cast<double*>(base + o_vals);
+    ca.p_mask = reinterpret_cast<uint8_t*>(base + o_mask);
+    ca.p_times = reinterpret_cast<double*>(base + o_times);
+    ca.p_coeffs = d_coeffs ? reinterpret_cast<double*>(base + o_coef) : nullptr;
+    ca.p_free = d_free ? reinterpret_cast<double*>(base + o_free) : nullptr;
+    ca.p_cost = d_cost ? reinterpret_cast<double*>(base + o_cost) : nullptr;
+    ca.p_n_free = d_nfree ? reinterpret_cast<int32_t*>(base + o_nfree) : nullptr;
+    ca.p_status = d_status ? reinterpret_cast<int32_t*>(base + o_status) : nullptr;
+    // entries beyond n_free are left zero (the scatter copies whole blocks)
+    if (d_free) MTG_HIP_TRY(ctx, hipMemsetAsync(base + o_free, 0, sizeof(double) * gV * hD, ctx->stream));
+  }
+  if (d_free && plan.n_in_place) MTG_HIP_TRY(ctx, hipMemsetAsync(d_free, 0, b_free, ctx->stream));
+
+  MTG_HIP_TRY(ctx, time_begin(ctx, false));
+  if (nG) MTG_HIP_TRY(ctx, mtg::launch_ragged_gather(ca, ctx->stream));
+  for (const mtg::RaggedGroup& g : plan.groups) {
+    // the group's arrays: slices of the CSR arrays at its first member, or of the packed arrays
+    const int64_t v0 = g.in_place ? plan.vo[(size_t)g.first] : plan.pvo[(size_t)g.first];
+    const int64_t s0 = v0 - g.first, t0 = g.first;
+    mtg::SolveArgs a{};
+    a.B = g.count;
+    a.K = g.K;
+    a.D = D;
+    a.r = r;
+    a.n_cand = 1;
+    if (g.in_place) {
+      a.values = d_vals + v0 * hD;
+      a.mask = d_mask + v0;
+      a.times = d_times + s0;
+      a.coeffs = d_coeffs ? d_coeffs + s0 * DN : nullptr;
+      a.free_out = d_free ? d_free + v0 * hD : nullptr;
+      a.n_free_out = d_nfree ? d_nfree + t0 : nullptr;
+      a.cost_out = d_cost ? d_cost + t0 : nullptr;
+      a.status = d_status ? d_status + t0 : nullptr;
+    } else {
+      a.values = ca.p_values + v0 * hD;
+      a.mask = ca.p_mask + v0;
+      a.times = ca.p_times + s0;
+      a.coeffs = ca.p_coeffs ? const_cast<double*>(ca.p_coeffs) + s0 * DN : nullptr;
+      a.free_out = ca.p_free ? const_cast<double*>(ca.p_free) + v0 * hD : nullptr;
+      a.n_free_out = ca.p_n_free ? const_cast<int32_t*>(ca.p_n_free) + t0 : nullptr;
+      a.cost_out = ca.p_cost ? const_cast<double*>(ca.p_cost) + t0 : nullptr;
+      a.status = ca.p_status ? const_cast<int32_t*>(ca.p_status) + t0 : nullptr;
+    }
+    if (split) {
+      MTG_HIP_TRY(ctx, mtg::launch_solve_split(N, a, ctx->workspace, ctx->stream));
+    } else {
+      if (mtg::solve_kernel(N, D, g.K, ksel, r, g.count) == MTG_KERNEL_DLX) {
+        a.work = static_cast<double*>(ctx->workspace);
+        a.work_bytes = (int64_t)ctx->workspace_bytes;
+      }
+      MTG_HIP_TRY(ctx, mtg::launch_solve(N, a, ctx->stream, ksel));
+    }
+  }
+  if (nG) MTG_HIP_TRY(ctx, mtg::launch_ragged_scatter(ca, ctx->stream));
+  MTG_HIP_TRY(ctx, time_end(ctx));
+  if (nG) {
+    if (!ctx->ragged_done) MTG_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ragged_done, hipEventDisableTiming));
+    MTG_HIP_TRY(ctx, hipEventRecord(ctx->ragged_done, ctx->stream));
+    ctx->ragged_done_pending = true;
+  }
+  return st.finish();
+}
+
 }  // namespace
 
 extern "C" {
@@ -853,6 +1057,15 @@ int mtg_destroy(mtg_ctx* ctx) {
   if (ctx->staging) (void)hipFree(ctx->staging);
   if (ctx->workspace) (void)hipFree(ctx->workspace);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+  if (ctx->ragged_done) {  // (a ragged call may have run on a stream that is no longer the context's)
+    if (ctx->ragged_done_pending) (void)hipEventSynchronize(ctx->ragged_done);
+    (void)hipEventDestroy(ctx->ragged_done);
+  }
+  for (auto& hb : ctx->ragged_host) {
+    if (hb.uploaded) (void)hipEventDestroy(hb.uploaded);
+    if (hb.p) (void)hipHostFree(hb.p);
+  }
+  if (ctx->ragged) (void)hipFree(ctx->ragged);
   destroy_pipe(ctx);
   destroy_events(ctx);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -902,6 +1115,37 @@ int mtg_solve_linear_batch(mtg_ctx* ctx, int N, int D, int K, int derivative_to_
   }
   return run_solve(ctx, N, D, K, derivative_to_optimize, batch, values, fixed_mask, times, coeffs,
                    free_out, n_free_out, cost_out, status, 1, nullptr, flags);
+}
+
+int mtg_solve_ragged_plan(int N, int D, int derivative_to_optimize, int64_t batch, const int32_t* seg_count,
+                          unsigned flags, int64_t* n_groups, int64_t* n_in_place, int64_t* total_segments) {
+  mtg::RaggedPlan plan;
+  const int rc = ragged_check_and_plan(nullptr, N, D, derivative_to_optimize, batch, seg_count, flags, &plan);
+  if (rc != MTG_OK) return rc;
+  if (n_groups) *n_groups = (int64_t)plan.groups.size();
+  if (n_in_place) *n_in_place = plan.n_in_place;
+  if (total_segments) *total_segments = plan.total_segments();
+  return MTG_OK;
+}
+
+int mtg_solve_linear_ragged_batch(mtg_ctx* ctx, int N, int D, int derivative_to_optimize, int64_t batch,
+                                  const int32_t* seg_count, const double* values, const uint8_t* fixed_mask,
+                                  const double* times, double* coeffs, double* free_out, int32_t* n_free_out,
+                                  double* cost_out, int32_t* status, unsigned flags) {
+  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
+  mtg::RaggedPlan plan;
+  const int rc = ragged_check_and_plan(ctx, N, D, derivative_to_optimize, batch, seg_count, flags, &plan);
+  if (rc != MTG_OK) return rc;
+  if (batch == 0) return MTG_OK;
+  if (!values || !fixed_mask || !times)
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "values, fixed_mask and times are required");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  try {
+    return run_solve_ragged(ctx, N, D, derivative_to_optimize, plan, values, fixed_mask, times, coeffs, free_out,
+                            n_free_out, cost_out, status, flags);
+  } catch (const std::bad_alloc&) {
+    return set_error(ctx, MTG_ERR_OUT_OF_MEMORY, "ragged solve: out of host memory");
+  }
 }
 
 int mtg_debug_fail_next_solve(mtg_ctx* ctx, int code) {

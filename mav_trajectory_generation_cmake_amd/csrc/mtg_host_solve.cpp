@@ -25,11 +25,13 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include <new>
 #include <thread>
 #include <vector>
 
 #include "mtg.h"
 #include "mtg_host_threads.h"
+#include "mtg_ragged_plan.h"
 #include "mtg_tables.inc"
 
 namespace {
@@ -401,6 +403,58 @@ extern "C" int mtg_host_solve_linear_batch(int N, int D, int K, int derivative_t
     for (int64_t b = 0; b < batch; ++b) one(b, s);
     return MTG_OK;
   }
+  // trajectories are independent: a shared counter hands out chunks of 64
+  std::atomic<int64_t> next{0};
+  auto worker = [&] {
+    Scratch s;
+    for (;;) {
+      const int64_t b0 = next.fetch_add(64);
+      if (b0 >= batch) break;
+      const int64_t b1 = b0 + 64 < batch ? b0 + 64 : batch;
+      for (int64_t b = b0; b < b1; ++b) one(b, s);
+    }
+  };
+  std::vector<std::thread> pool;
+  pool.reserve(nt - 1);
+  for (int t = 1; t < nt; ++t) pool.emplace_back(worker);
+  worker();
+  for (auto& t : pool) t.join();
+  return MTG_OK;
+}
+
+// Host path of mtg_solve_linear_ragged_batch: the plan's CSR offsets, then every trajectory solved on
+// its own blocks by the code above (what mtg_host_solve_linear_batch runs for a batch of one), threaded
+// over trajectories.
+extern "C" int mtg_host_solve_linear_ragged_batch(int N, int D, int derivative_to_optimize, int64_t batch,
+                                                  const int32_t* seg_count, const double* values,
+                                                  const uint8_t* fixed_mask, const double* times, double* coeffs,
+                                                  double* free_out, int32_t* n_free_out, double* cost_out,
+                                                  int32_t* status, int threads) {
+  if (N < 2 || N > 12 || (N % 2)) return MTG_ERR_UNSUPPORTED_N;
+  if (derivative_to_optimize < 0 || derivative_to_optimize > N / 2 - 1) return MTG_ERR_BAD_DERIVATIVE;
+  if (D < 1 || batch < 0) return MTG_ERR_SIZE_MISMATCH;
+  if (batch == 0) return MTG_OK;
+  if (!seg_count) return MTG_ERR_INVALID_ARGUMENT;
+  mtg::RaggedPlan plan;
+  try {
+    const int rc = mtg::ragged_plan(batch, seg_count, &plan);
+    if (rc != MTG_OK) return rc;
+  } catch (const std::bad_alloc&) {
+    return MTG_ERR_OUT_OF_MEMORY;
+  }
+  if (!values || !fixed_mask || !times) return MTG_ERR_INVALID_ARGUMENT;
+  const SolveFn fn = solver_for(N);
+  const size_t hD = (size_t)(N / 2) * D, DN = (size_t)D * N;
+  auto one = [&](int64_t b, Scratch& s) {
+    const size_t v0 = (size_t)plan.vo[(size_t)b], s0 = (size_t)plan.so(b);
+    const int32_t st = fn(D, seg_count[b], derivative_to_optimize, values + v0 * hD, fixed_mask + v0, times + s0,
+                          coeffs ? coeffs + s0 * DN : nullptr, free_out ? free_out + v0 * hD : nullptr,
+                          n_free_out ? n_free_out + b : nullptr, cost_out ? cost_out + b : nullptr, s);
+    if (status) status[b] = st;
+  };
+  int nt = threads > 0 ? threads : mtg::usable_cpus();
+  if (nt < 1) nt = 1;
+  if ((int64_t)nt > batch) nt = (int)batch;
   // trajectories are independent: a shared counter hands out chunks of 64
   std::atomic<int64_t> next{0};
   auto worker = [&] {

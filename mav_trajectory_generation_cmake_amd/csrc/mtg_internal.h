@@ -81,6 +81,33 @@ hipError_t launch_solve_dlx(int N, const SolveArgs& a, hipStream_t stream);
 size_t split_workspace_bytes(int N, int D, int K, int64_t B);
 hipError_t launch_solve_split(int N, const SolveArgs& a, void* workspace, hipStream_t stream);
 
+// The copy kernels of the ragged solve (mtg_ragged.hip).  One record per gathered trajectory, record j
+// for the j-th trajectory of the packed arrays: vertex offsets in the caller's CSR arrays and in the
+// packed ones (the segment offsets are src_v - b and dst_v - j), the batch index and K.
+struct RaggedRec {
+  int64_t src_v, dst_v, b;
+  int32_t K, reserved;
+};
+struct RaggedCopyArgs {
+  const RaggedRec* recs;  // [n]
+  int64_t n;
+  int hD, DN;             // (N / 2) D and D N
+  // the caller's CSR arrays (gather reads the first three, scatter writes the others; nullable outputs)
+  const double* values;
+  const uint8_t* mask;
+  const double* times;
+  double *coeffs, *free, *cost;
+  int32_t *n_free, *status;
+  // the packed arrays (gather writes the first three, scatter reads the others)
+  double* p_values;
+  uint8_t* p_mask;
+  double* p_times;
+  const double *p_coeffs, *p_free, *p_cost;
+  const int32_t *p_n_free, *p_status;
+};
+hipError_t launch_ragged_gather(const RaggedCopyArgs& a, hipStream_t stream);
+hipError_t launch_ragged_scatter(const RaggedCopyArgs& a, hipStream_t stream);
+
 // cost / gradient of fixed vertex derivatives at candidate times (mtg_cost.hip)
 size_t cost_lds_bytes(int N, int D, int K);
 hipError_t launch_cost_at_times(int N, int r, const double* values, const uint8_t* mask, const double* times,

@@ -17,7 +17,9 @@ bool reg_geometry(int N, int D, int K, int* lanes_per_traj, size_t* lds_bytes) {
   // G_v columns take H * KMAX doubles per lane: beyond ~50 the 2-waves-per-SIMD kernel spills
   // (N=12, K > 8); the wide bucket (N = 12, K <= 20) keeps G in LDS instead (Forward::GLDS)
   const int km = reg_kmax(K);
-  if (km < 0 || (H * km > 50 && !(N == 12 && km == kRegKMaxWide))) return false;
+  // (the wide bucket is instantiated for N = 12 alone: N = 2 / 4 with 12 < K <= 20 passed the register
+  // bound, was reported as the column kernel and then failed to launch; it is the general kernel's)
+  if (km < 0 || (km == kRegKMaxWide && N != 12) || (H * km > 50 && !(N == 12 && km == kRegKMaxWide))) return false;
   int lc = 8;  // lanes per chain: h column lanes + D dimension lanes
   while (lc < H + D) lc *= 2;
   const int lg = kTwist ? 2 * lc : lc;  // twisted: two chains per trajectory

@@ -203,6 +203,71 @@ class Context:
         nat.check(rc, self.handle)
         return out
 
+    def solve_linear_ragged_batch(self, N, r, values, mask, times, seg_count, coeffs=None, free=None, n_free=None,
+                                  cost=None, status=None, split=False, asynchronous=False, general=False, dl=False,
+                                  column=False):
+        """Solve a batch whose trajectories have different segment counts (mtg_solve_linear_ragged_batch).
+
+        The arrays are the CSR arrays of include/mtg.h (pack_ragged builds them): values [sum V][N/2][D],
+        mask [sum V], times [sum K], numpy or torch-device; seg_count [B] is a host array (numpy or a
+        list) either way.  Returns a dict of the outputs: coeffs [sum K][D][N], free (flat, D N/2 sum V
+        doubles), n_free / cost / status [B]; split_ragged gives per-trajectory views.  The want-flags are
+        those of solve_linear_batch; coeffs=False leaves the coefficients out."""
+        dev = _is_torch(values) and values.is_cuda
+        seg_count = np.ascontiguousarray(seg_count, dtype=np.int32)
+        B = int(seg_count.shape[0])
+        totS = int(seg_count.sum(dtype=np.int64))
+        totV = totS + B
+        h = N // 2
+        assert values.ndim == 3 and values.shape[1] == h, "values must be [sum V][N/2][D]"
+        D = int(values.shape[2])
+        assert int(values.shape[0]) == totV and tuple(mask.shape) == (totV,) and tuple(times.shape) == (totS,)
+        out = {}
+
+        def alloc(name, arr, shape, dtype):
+            if arr is None or arr is False:
+                return None
+            if arr is True:
+                if dev:
+                    import torch
+                    tdt = {np.float64: torch.float64, np.int32: torch.int32}[dtype]
+                    arr = torch.empty(shape, dtype=tdt, device=values.device)
+                else:
+                    arr = np.empty(shape, dtype=dtype)
+            out[name] = arr
+            return arr
+
+        coeffs = alloc("coeffs", True if coeffs is None else coeffs, (totS, D, N), np.float64)
+        free = alloc("free", free, (totV * h * D,), np.float64)
+        n_free = alloc("n_free", n_free, (B,), np.int32)
+        cost = alloc("cost", cost, (B,), np.float64)
+        status = alloc("status", status, (B,), np.int32)
+        flags = 0
+        if dev:
+            import torch
+            flags |= nat.MTG_FLAG_DEVICE_PTRS
+            self.set_stream(torch.cuda.current_stream(values.device).cuda_stream)
+            if asynchronous:
+                flags |= nat.MTG_FLAG_ASYNC
+        else:
+            values = np.ascontiguousarray(values, dtype=np.float64)
+            mask = np.ascontiguousarray(mask, dtype=np.uint8)
+            times = np.ascontiguousarray(times, dtype=np.float64)
+            self.reset_stream()
+        if split:
+            flags |= nat.MTG_FLAG_SPLIT_KERNELS
+        if general:
+            flags |= nat.MTG_FLAG_GENERAL_KERNEL
+        if dl:
+            flags |= nat.MTG_FLAG_DL_KERNEL
+        if column:
+            flags |= nat.MTG_FLAG_COLUMN_KERNEL
+        rc = self._lib.mtg_solve_linear_ragged_batch(self.handle, N, D, r, B, _addr(seg_count), _addr(values),
+                                                     _addr(mask), _addr(times), _addr(coeffs), _addr(free),
+                                                     _addr(n_free), _addr(cost), _addr(status), flags)
+        nat.check(rc, self.handle)
+        return out
+
     def time_sweep_batch(self, N, r, values, mask, times, scales, cost=None, status=None,
                          asynchronous=False, split=False, dl=False, column=False, general=False):
         dev = _is_torch(values) and values.is_cuda
@@ -1216,6 +1281,101 @@ def host_solve_linear_batch(N, r, values, mask, times, free=False, n_free=False,
                                               _addr(out["coeffs"]), _addr(out.get("free")),
                                               _addr(out.get("n_free")), _addr(out.get("cost")),
                                               _addr(out.get("status")), threads))
+    return out
+
+
+# --------------------------------------------------------------------- ragged
+def ragged_offsets(seg_count):
+    """(vo, so) of the CSR layout (include/mtg.h, mtg_solve_linear_ragged_batch): int64 arrays of B + 1
+    entries, vo[b] = sum_{j<b} (K_j + 1) and so[b] = sum_{j<b} K_j; the last entries are the totals."""
+    k = np.asarray(seg_count, dtype=np.int64).reshape(-1)
+    so = np.concatenate([[0], np.cumsum(k)]).astype(np.int64)
+    return so + np.arange(len(k) + 1, dtype=np.int64), so
+
+
+def pack_ragged(problems):
+    """CSR arrays of a list of problems, each (values [V][N/2][D], mask [V], times [K]) with V = K + 1:
+    returns (values [sum V][N/2][D], mask [sum V], times [sum K], seg_count [B] int32)."""
+    problems = list(problems)
+    for v, m, t in problems:
+        assert v.ndim == 3 and m.shape == (v.shape[0],) and t.shape == (v.shape[0] - 1,) and len(t) >= 1
+    seg_count = np.array([len(t) for _, _, t in problems], dtype=np.int32)
+    if not problems:
+        return np.zeros((0, 0, 0)), np.zeros((0,), np.uint8), np.zeros((0,)), seg_count
+    values = np.ascontiguousarray(np.concatenate([v for v, _, _ in problems]), dtype=np.float64)
+    mask = np.ascontiguousarray(np.concatenate([m for _, m, _ in problems]), dtype=np.uint8)
+    times = np.ascontiguousarray(np.concatenate([t for _, _, t in problems]), dtype=np.float64)
+    return values, mask, times, seg_count
+
+
+_RAGGED_KINDS = {"values": "vertex", "mask": "vertex", "times": "segment", "coeffs": "segment", "free": "free",
+                 "n_free": "trajectory", "cost": "trajectory", "status": "trajectory"}
+
+
+def split_ragged(array, seg_count, kind, D=None):
+    """Per-trajectory views (no copies) of one CSR array of a ragged batch, numpy or torch.  kind names
+    the array: "values" -> [V_b][N/2][D], "mask" -> [V_b], "times" -> [K_b], "coeffs" -> [K_b][D][N],
+    "free" -> [D][V_b N/2] (needs D), "n_free" / "cost" / "status" -> the entry of b."""
+    what = _RAGGED_KINDS[kind]
+    vo, so = ragged_offsets(seg_count)
+    B = len(vo) - 1
+    if what == "trajectory":
+        return [array[b] for b in range(B)]
+    if what == "free":
+        assert D is not None, "split_ragged(..., 'free') needs D"
+        flat = array.reshape(-1)
+        hD = int(flat.shape[0]) // max(int(vo[-1]), 1)
+        return [flat[hD * int(vo[b]):hD * int(vo[b + 1])].reshape(D, -1) for b in range(B)]
+    off = vo if what == "vertex" else so
+    return [array[int(off[b]):int(off[b + 1])] for b in range(B)]
+
+
+def solve_ragged_plan(N, D, r, seg_count, split=False, general=False, dl=False, column=False):
+    """The plan mtg_solve_linear_ragged_batch makes for these segment counts (mtg_solve_ragged_plan; no
+    device work): a dict with n_groups (distinct K), n_in_place (trajectories of groups that are one run of
+    the batch, solved on slices of the caller's arrays; == B for a batch sorted by K) and total_segments."""
+    lib = nat.load()
+    addr, B = None, 0
+    if seg_count is not None:
+        seg_count = np.ascontiguousarray(seg_count, dtype=np.int32)
+        addr, B = _addr(seg_count), int(seg_count.shape[0])
+    flags = ((nat.MTG_FLAG_SPLIT_KERNELS if split else 0) | (nat.MTG_FLAG_GENERAL_KERNEL if general else 0) |
+             (nat.MTG_FLAG_DL_KERNEL if dl else 0) | (nat.MTG_FLAG_COLUMN_KERNEL if column else 0))
+    g, p, s = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    nat.check(lib.mtg_solve_ragged_plan(N, D, r, B, addr, flags, ctypes.byref(g), ctypes.byref(p), ctypes.byref(s)))
+    return {"n_groups": g.value, "n_in_place": p.value, "total_segments": s.value}
+
+
+def host_solve_linear_ragged_batch(N, r, values, mask, times, seg_count, free=False, n_free=False, cost=False,
+                                   status=False, threads=1):
+    """The library's host (CPU) path of Context.solve_linear_ragged_batch
+    (mtg_host_solve_linear_ragged_batch): the same CSR arrays and outputs, no GPU.  Every trajectory's
+    outputs are the bytes host_solve_linear_batch gives for it alone."""
+    lib = nat.load()
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    mask = np.ascontiguousarray(mask, dtype=np.uint8)
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    seg_count = np.ascontiguousarray(seg_count, dtype=np.int32)
+    B = int(seg_count.shape[0])
+    totS = int(seg_count.sum(dtype=np.int64))
+    totV = totS + B
+    h = N // 2
+    assert values.ndim == 3 and values.shape[1] == h, "values must be [sum V][N/2][D]"
+    D = int(values.shape[2])
+    assert values.shape[0] == totV and mask.shape == (totV,) and times.shape == (totS,)
+    out = {"coeffs": np.empty((totS, D, N))}
+    if free:
+        out["free"] = np.empty((totV * h * D,))
+    if n_free:
+        out["n_free"] = np.empty((B,), np.int32)
+    if cost:
+        out["cost"] = np.empty((B,))
+    if status:
+        out["status"] = np.empty((B,), np.int32)
+    nat.check(lib.mtg_host_solve_linear_ragged_batch(N, D, r, B, _addr(seg_count), _addr(values), _addr(mask),
+                                                     _addr(times), _addr(out["coeffs"]), _addr(out.get("free")),
+                                                     _addr(out.get("n_free")), _addr(out.get("cost")),
+                                                     _addr(out.get("status")), threads))
     return out
 
 
