@@ -7,7 +7,8 @@
 // derivative k fixed), times [B][K], coeffs [B][K][D][N].  Pass MTG_FLAG_DEVICE_PTRS to hand over
 // device pointers (inputs already in HBM); host pointers are staged by the library.
 // solveRagged takes problems of different segment counts in one call (CSR arrays, include/mtg.h
-// mtg_solve_linear_ragged_batch): the one entry here that is not tied to the object's K.
+// mtg_solve_linear_ragged_batch), and evaluateAtRagged / minMaxMagnitudeRagged consume its coefficients
+// in the same layout: the entries here that are not tied to the object's K.
 //
 // Several devices: construct with a device list (e.g. allDevices()).  A host-array solve() is then
 // one mtg_solve_linear_batch_multi call: contiguous shards of the batch, one host thread and one
@@ -321,6 +322,25 @@ class BatchPolynomialOptimization {
                                 n_derivatives, out, in_range, status, flags),
           ctx_, "mtg_evaluate_at_batch");
   }
+  // evaluateAt and minMaxMagnitude for trajectories of different segment counts
+  // (mtg_evaluate_at_ragged_batch, mtg_min_max_magnitude_ragged_batch): coeffs [sum K][D][N] and times
+  // [sum K] are the CSR arrays solveRagged writes and takes, seg_count [batch] a host array also with
+  // MTG_FLAG_DEVICE_PTRS; the other arguments are those of the uniform members.  Every trajectory's
+  // outputs are the bytes the uniform member gives for it alone.  The object's `segments` is not used.
+  void evaluateAtRagged(int64_t batch, const int32_t* seg_count, const double* coeffs, const double* times,
+                        const double* t_query, int64_t t_stride, int64_t M, int derivative_begin, int n_derivatives,
+                        double* out, uint8_t* in_range = nullptr, int32_t* status = nullptr, unsigned flags = 0) {
+    check(mtg_evaluate_at_ragged_batch(ctx_, N, D_, batch, seg_count, coeffs, times, t_query, t_stride, M,
+                                       derivative_begin, n_derivatives, out, in_range, status, flags),
+          ctx_, "mtg_evaluate_at_ragged_batch");
+  }
+  void minMaxMagnitudeRagged(int64_t batch, const int32_t* seg_count, const double* coeffs, const double* times,
+                             int derivative, uint32_t dimension_mask, mtg_extremum* minimum, mtg_extremum* maximum,
+                             unsigned flags = 0) {
+    check(mtg_min_max_magnitude_ragged_batch(ctx_, N, D_, batch, seg_count, coeffs, times, derivative, dimension_mask,
+                                             minimum, maximum, flags),
+          ctx_, "mtg_min_max_magnitude_ragged_batch");
+  }
 
  private:
   int D_, K_, r_;
@@ -457,6 +477,42 @@ inline void evaluateAt(int D, int K, int64_t batch, const double* coeffs, const 
     check(mtg_host_evaluate_at_batch(N, D, K, batch, coeffs, times, t_query, t_stride, M, derivative_begin,
                                      n_derivatives, out, in_range, status, 1),
           nullptr, "mtg_host_evaluate_at_batch");
+  }
+}
+
+// evaluateAt<N> and Trajectory::computeMinMaxMagnitude for trajectories of different segment counts in
+// the CSR layout (coeffs [sum K][D][N], times [sum K], seg_count [batch]), without a
+// BatchPolynomialOptimization object: on the library's host paths unless the execution policy is
+// kDevice, as evaluateAt.  Host pointers.
+template <int N>
+inline void evaluateAtRagged(int D, int64_t batch, const int32_t* seg_count, const double* coeffs, const double* times,
+                             const double* t_query, int64_t t_stride, int64_t M, int derivative_begin,
+                             int n_derivatives, double* out, uint8_t* in_range = nullptr, int32_t* status = nullptr) {
+  if (singleOnDevice()) {
+    mtg_ctx* ctx = defaultContext();
+    check(mtg_evaluate_at_ragged_batch(ctx, N, D, batch, seg_count, coeffs, times, t_query, t_stride, M,
+                                       derivative_begin, n_derivatives, out, in_range, status, 0),
+          ctx, "mtg_evaluate_at_ragged_batch");
+  } else {
+    check(mtg_host_evaluate_at_ragged_batch(N, D, batch, seg_count, coeffs, times, t_query, t_stride, M,
+                                            derivative_begin, n_derivatives, out, in_range, status, 1),
+          nullptr, "mtg_host_evaluate_at_ragged_batch");
+  }
+}
+
+template <int N>
+inline void minMaxMagnitudeRagged(int D, int64_t batch, const int32_t* seg_count, const double* coeffs,
+                                  const double* times, int derivative, uint32_t dimension_mask, mtg_extremum* minimum,
+                                  mtg_extremum* maximum) {
+  if (singleOnDevice()) {
+    mtg_ctx* ctx = defaultContext();
+    check(mtg_min_max_magnitude_ragged_batch(ctx, N, D, batch, seg_count, coeffs, times, derivative, dimension_mask,
+                                             minimum, maximum, 0),
+          ctx, "mtg_min_max_magnitude_ragged_batch");
+  } else {
+    check(mtg_host_min_max_magnitude_ragged_batch(N, D, batch, seg_count, coeffs, times, derivative, dimension_mask,
+                                                  minimum, maximum, 1),
+          nullptr, "mtg_host_min_max_magnitude_ragged_batch");
   }
 }
 

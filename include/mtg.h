@@ -54,7 +54,10 @@ extern "C" {
                                5, additive: + mtg_evaluate_at_batch, mtg_host_evaluate_at_batch,
                                     mtg_evaluate_at_path
                                5, additive: + mtg_solve_linear_ragged_batch, mtg_host_solve_linear_ragged_batch,
-                                    mtg_solve_ragged_plan */
+                                    mtg_solve_ragged_plan
+                               5, additive: + mtg_evaluate_at_ragged_batch, mtg_evaluate_at_ragged_path,
+                                    mtg_host_evaluate_at_ragged_batch, mtg_min_max_magnitude_ragged_batch,
+                                    mtg_host_min_max_magnitude_ragged_batch */
 
 /* Call-level return codes. */
 #define MTG_OK 0
@@ -319,6 +322,32 @@ int mtg_evaluate_at_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, cons
  * M >= max(32, K) and the staged block fits LDS -- or a negative MTG_ERR_*.  No device work. */
 int mtg_evaluate_at_path(int N, int D, int K, int64_t M, int n_derivatives);
 
+/* mtg_evaluate_at_batch for a batch whose trajectories have different segment counts, in the CSR
+ * layout of mtg_solve_linear_ragged_batch (so[b] = sum_{j<b} seg_count[j], 64-bit):
+ *   coeffs [so[b] .. so[b] + K_b][D][N], times [so[b] .. so[b] + K_b]   (as the ragged solve writes them)
+ *   t_query, out [B][M][n_derivatives][D], in_range_out [B][M], status [B]: as in the uniform call
+ *   seg_count [B]: a HOST array also with MTG_FLAG_DEVICE_PTRS, read during the call and not kept
+ * Semantics: per trajectory and query exactly the text of mtg_evaluate_at_batch with K = K_b -- the
+ * segment search, the beyond / end / NaN / negative-time rules, the unfused Horner, MTG_TRAJ_BAD_TIME
+ * giving NaN rows -- so every output byte of trajectory b equals what mtg_evaluate_at_batch writes for
+ * that trajectory alone, whatever the order of the batch.
+ * The CSR indirection is in the kernels: the segment offsets [B + 1] are computed on
+ * the host and uploaded (8 (B + 1) bytes), no coefficient is copied.  The mapping is
+ * mtg_evaluate_at_ragged_path(N, D, max K_b, M, n_derivatives): one rule, from the shape alone.
+ * Flags as in the uniform call; a host-pointer call stages the CSR arrays whole.  Two MTG_FLAG_ASYNC
+ * ragged calls of any kind on one context, with different seg_count, may follow each other without a
+ * synchronisation between them.
+ * Errors, all before any device work: those of mtg_evaluate_at_batch on N, D, batch, M, t_stride and
+ * the derivative arguments; MTG_ERR_INVALID_ARGUMENT for seg_count == NULL with batch > 0;
+ * MTG_ERR_SIZE_MISMATCH for any seg_count[b] < 1.  batch == 0 or M == 0: MTG_OK, nothing written. */
+int mtg_evaluate_at_ragged_batch(mtg_ctx* ctx, int N, int D, int64_t batch, const int32_t* seg_count,
+                                 const double* coeffs, const double* times, const double* t_query, int64_t t_stride,
+                                 int64_t M, int derivative_begin, int n_derivatives, double* out,
+                                 uint8_t* in_range_out, int32_t* status, unsigned flags);
+/* The kernel (MTG_EVALUATE_AT_*) mtg_evaluate_at_ragged_batch runs for a batch whose largest segment
+ * count is K_max: mtg_evaluate_at_path(N, D, K_max, M, n_derivatives).  No device work. */
+int mtg_evaluate_at_ragged_path(int N, int D, int K_max, int64_t M, int n_derivatives);
+
 /* Batched segment-time sweep (the nonlinear time-allocation objective,
  * polynomial_optimization_nonlinear_impl.h:765-832 via updateSegmentTimes +
  * solveLinear + computeCost): for each trajectory b and candidate c the
@@ -398,6 +427,27 @@ typedef struct mtg_extremum {
 int mtg_min_max_magnitude_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* coeffs,
                                 const double* times, int derivative, uint32_t dimension_mask,
                                 mtg_extremum* minimum, mtg_extremum* maximum, unsigned flags);
+
+/* mtg_min_max_magnitude_batch for a batch whose trajectories have different segment counts, in the
+ * CSR layout of mtg_solve_linear_ragged_batch: coeffs [so[b] .. so[b] + K_b][D][N],
+ * times [so[b] .. so[b] + K_b], minimum / maximum [B] (either may be NULL); seg_count [B] is a HOST
+ * array also with MTG_FLAG_DEVICE_PTRS.  Every output byte of trajectory b equals what
+ * mtg_min_max_magnitude_batch writes for that trajectory alone.
+ * The extrema kernel's rounding order depends on the block geometry its launcher derives from K, so
+ * this entry follows the ragged solve: the same host-side plan; a K-group that is one
+ * run of the batch goes through the uniform launcher in place, on slices of the caller's arrays; the
+ * coefficients and times of every other group are gathered into packed arrays by one kernel, the
+ * uniform launcher runs there, and one kernel moves the results to minimum[b] / maximum[b].  One
+ * launch per group in ascending K, one stream, no host synchronisation in between; a batch sorted by
+ * K copies nothing.
+ * Errors, all before any device work: those of the uniform call on N, D, batch, derivative and
+ * dimension_mask; MTG_ERR_INVALID_ARGUMENT for seg_count == NULL with batch > 0;
+ * MTG_ERR_SIZE_MISMATCH for any seg_count[b] < 1; MTG_ERR_TOO_LARGE for any seg_count[b] > 256.
+ * batch == 0: MTG_OK. */
+int mtg_min_max_magnitude_ragged_batch(mtg_ctx* ctx, int N, int D, int64_t batch, const int32_t* seg_count,
+                                       const double* coeffs, const double* times, int derivative,
+                                       uint32_t dimension_mask, mtg_extremum* minimum, mtg_extremum* maximum,
+                                       unsigned flags);
 
 /* ---- Collision term of the nonlinear objective (kOptimizeFreeConstraintsAndCollision[AndTime]).
  *
@@ -935,6 +985,20 @@ int mtg_host_min_max_magnitude_batch(int N, int D, int K, int64_t batch, const d
 int mtg_host_evaluate_at_batch(int N, int D, int K, int64_t batch, const double* coeffs, const double* times,
                                const double* t_query, int64_t t_stride, int64_t M, int derivative_begin,
                                int n_derivatives, double* out, uint8_t* in_range_out, int32_t* status, int threads);
+
+/* Host (CPU) paths of mtg_evaluate_at_ragged_batch and mtg_min_max_magnitude_ragged_batch, no context
+ * and no GPU needed: the scalar code behind the two host entries above on each trajectory's blocks of
+ * the CSR arrays, so a trajectory's outputs are the bytes those entries write for it alone.  Threaded
+ * over trajectories; threads <= 0: mtg_host_default_threads().  All host pointers; the call-level
+ * errors of the device calls except MTG_ERR_TOO_LARGE. */
+int mtg_host_evaluate_at_ragged_batch(int N, int D, int64_t batch, const int32_t* seg_count, const double* coeffs,
+                                      const double* times, const double* t_query, int64_t t_stride, int64_t M,
+                                      int derivative_begin, int n_derivatives, double* out, uint8_t* in_range_out,
+                                      int32_t* status, int threads);
+int mtg_host_min_max_magnitude_ragged_batch(int N, int D, int64_t batch, const int32_t* seg_count,
+                                            const double* coeffs, const double* times, int derivative,
+                                            uint32_t dimension_mask, mtg_extremum* minimum, mtg_extremum* maximum,
+                                            int threads);
 
 /* ---- Host utilities (no GPU): the reference's synthetic-input generators,
  * bit-exact with libstdc++ <random>, packed straight into the ABI layout.

@@ -129,6 +129,20 @@ _SIGNATURES = {
     "mtg_host_solve_linear_ragged_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                                           _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
                                                           _c_dp, ctypes.c_int]),
+    "mtg_evaluate_at_ragged_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _c_dp,
+                                                    _c_dp, _c_dp, _c_dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                                    ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_uint]),
+    "mtg_evaluate_at_ragged_path": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                   ctypes.c_int]),
+    "mtg_host_evaluate_at_ragged_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, _c_dp, _c_dp,
+                                                         _c_dp, _c_dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                                         ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mtg_min_max_magnitude_ragged_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                          _c_dp, _c_dp, _c_dp, ctypes.c_int, ctypes.c_uint32, _c_dp,
+                                                          _c_dp, ctypes.c_uint]),
+    "mtg_host_min_max_magnitude_ragged_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, _c_dp, _c_dp,
+                                                               _c_dp, ctypes.c_int, ctypes.c_uint32, _c_dp, _c_dp,
+                                                               ctypes.c_int]),
     "mtg_shard_range": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
                                        ctypes.POINTER(ctypes.c_int64)]),
     "mtg_solve_linear_batch_multi": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -336,6 +350,15 @@ def evaluate_at_path(N, D, K, M, n_derivatives=1):
     """The kernel mtg_evaluate_at_batch runs for this shape (mtg_evaluate_at_path): MTG_EVALUATE_AT_LANE or
     MTG_EVALUATE_AT_STAGED.  Depends on the shape only."""
     code = load().mtg_evaluate_at_path(N, D, K, M, n_derivatives)
+    if code < 0:
+        raise MTGError(code, status_string(code))
+    return code
+
+
+def evaluate_at_ragged_path(N, D, K_max, M, n_derivatives=1):
+    """The kernel mtg_evaluate_at_ragged_batch runs for a batch whose largest segment count is K_max
+    (mtg_evaluate_at_ragged_path): the rule of evaluate_at_path at K = K_max."""
+    code = load().mtg_evaluate_at_ragged_path(N, D, K_max, M, n_derivatives)
     if code < 0:
         raise MTGError(code, status_string(code))
     return code

@@ -813,6 +813,179 @@ int ragged_check_and_plan(mtg_ctx* ctx, int N, int D, int r, int64_t batch, cons
   return MTG_OK;
 }
 
+// What the ragged entries share around ctx->ragged (the device copy of a call's small host-made
+// arrays -- plan records, segment offsets -- and the packed arrays of gathered groups).
+//
+// An earlier ragged call may have run on another stream (mtg_set_stream): the next one reuses its
+// buffer, so it waits for that call's last kernel first (ragged_wait_last), and records its own last
+// kernel when it used the buffer (ragged_mark_last).
+int ragged_wait_last(mtg_ctx* ctx) {
+  if (ctx->ragged_done_pending) MTG_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ragged_done, 0));
+  return MTG_OK;
+}
+
+int ragged_mark_last(mtg_ctx* ctx) {
+  if (!ctx->ragged_done) MTG_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ragged_done, hipEventDisableTiming));
+  MTG_HIP_TRY(ctx, hipEventRecord(ctx->ragged_done, ctx->stream));
+  ctx->ragged_done_pending = true;
+  return MTG_OK;
+}
+
+// The upload of `bytes` host-made bytes to dst (in ctx->ragged): fill(p) writes them into the pinned
+// buffer whose turn it is, once the event behind that buffer's last upload has fired, and the copy is
+// queued on ctx->stream.  The copy outlives an MTG_FLAG_ASYNC call, hence pinned memory the context
+// owns; two buffers taken in turn, so that two such calls with different seg_count may follow each
+// other without a synchronisation.
+template <class Fill>
+int ragged_upload(mtg_ctx* ctx, size_t bytes, void* dst, Fill fill) {
+  mtg_ctx::RaggedHost& hb = ctx->ragged_host[ctx->ragged_turn];
+  ctx->ragged_turn ^= 1;
+  if (!hb.uploaded) MTG_HIP_TRY(ctx, hipEventCreateWithFlags(&hb.uploaded, hipEventDisableTiming));
+  if (hb.pending) {
+    MTG_HIP_TRY(ctx, hipEventSynchronize(hb.uploaded));
+    hb.pending = false;
+  }
+  if (hb.bytes < bytes) {
+    if (hb.p) MTG_HIP_TRY(ctx, hipHostFree(hb.p));
+    hb.p = nullptr;
+    hb.bytes = 0;
+    const size_t want = std::max<size_t>(bytes + bytes / 2, 4096);
+    MTG_HIP_TRY(ctx, hipHostMalloc(&hb.p, want, hipHostMallocDefault));
+    hb.bytes = want;
+  }
+  fill(hb.p);
+  MTG_HIP_TRY(ctx, hipMemcpyAsync(dst, hb.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+  MTG_HIP_TRY(ctx, hipEventRecord(hb.uploaded, ctx->stream));
+  hb.pending = true;
+  return MTG_OK;
+}
+
+// one RaggedRec per gathered trajectory of the plan, to dst
+int ragged_upload_records(mtg_ctx* ctx, const mtg::RaggedPlan& plan, void* dst) {
+  const size_t nG = plan.members.size();
+  return ragged_upload(ctx, sizeof(mtg::RaggedRec) * nG, dst, [&](void* p) {
+    mtg::RaggedRec* recs = static_cast<mtg::RaggedRec*>(p);
+    for (size_t j = 0; j < nG; ++j) {
+      const int64_t b = plan.members[j];
+      recs[j] = mtg::RaggedRec{plan.vo[(size_t)b], plan.pvo[j], b, (int32_t)(plan.vo[(size_t)b + 1] - plan.vo[(size_t)b] - 1), 0};
+    }
+  });
+}
+
+// The seg_count checks of mtg_evaluate_at_ragged_batch, after its checks on N, D, batch, M and the
+// derivative arguments (the min / max entry gets the same two errors from its plan): seg_count present,
+// every entry >= 1.  *k_max receives the largest and *so the segment offsets [batch + 1].  batch == 0:
+// nothing is checked and *so stays empty.
+int ragged_check_counts(mtg_ctx* ctx, int64_t batch, const int32_t* seg_count, int* k_max, std::vector<int64_t>* so) {
+  *k_max = 0;
+  if (batch == 0) return MTG_OK;
+  if (!seg_count) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "seg_count is required (a host array)");
+  so->assign((size_t)batch + 1, 0);
+  for (int64_t b = 0; b < batch; ++b) {
+    if (seg_count[b] < 1) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "every seg_count must be >= 1");
+    *k_max = std::max<int>(*k_max, seg_count[b]);
+    (*so)[(size_t)b + 1] = (*so)[(size_t)b] + seg_count[b];
+  }
+  return MTG_OK;
+}
+
+// Body of mtg_evaluate_at_ragged_batch: the segment offsets to ctx->ragged, then one
+// launch of the ragged kernels on the caller's CSR arrays; nothing is copied on the device.
+int run_evaluate_at_ragged(mtg_ctx* ctx, int N, int D, int k_max, const std::vector<int64_t>& so, const double* coeffs,
+                           const double* times, const double* t_query, int64_t t_stride, int64_t M, int k0, int nd,
+                           double* out, uint8_t* in_range_out, int32_t* status, unsigned flags) {
+  MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t nB = so.size() - 1, nM = (size_t)M, totS = (size_t)so.back();
+  const double *d_coef, *d_times, *d_tq;
+  double* d_out;
+  uint8_t* d_in;
+  int32_t* d_status;
+  Staged st(ctx, flags);
+  st.in(&d_coef, coeffs, sizeof(double) * totS * D * N);
+  st.in(&d_times, times, sizeof(double) * totS);
+  st.in(&d_tq, t_query, sizeof(double) * (t_stride ? (nB - 1) * (size_t)t_stride + nM : nM));
+  st.out(&d_out, out, sizeof(double) * nB * nM * nd * D);
+  st.out(&d_in, in_range_out, nB * nM);
+  st.out(&d_status, status, sizeof(int32_t) * nB);
+  if (int rc = ragged_wait_last(ctx)) return rc;
+  if (int rc = st.upload()) return rc;
+  const size_t b_so = sizeof(int64_t) * so.size();
+  MTG_HIP_TRY(ctx, ensure(&ctx->ragged, &ctx->ragged_bytes, align_up(b_so)));
+  if (int rc = ragged_upload(ctx, b_so, ctx->ragged, [&](void* p) { std::memcpy(p, so.data(), b_so); })) return rc;
+  MTG_HIP_TRY(ctx, time_begin(ctx));
+  MTG_HIP_TRY(ctx, mtg::launch_evaluate_at_ragged(N, D, k_max, (int64_t)nB, static_cast<const int64_t*>(ctx->ragged),
+                                                  d_coef, d_times, d_tq, t_stride, M, k0, nd, d_out, d_in, d_status,
+                                                  ctx->stream));
+  MTG_HIP_TRY(ctx, time_end(ctx));
+  if (int rc = ragged_mark_last(ctx)) return rc;
+  return st.finish();
+}
+
+// Body of mtg_min_max_magnitude_ragged_batch.  The extrema kernel's bits depend on
+// the block geometry its launcher derives from K, so every K-group goes through the unchanged uniform
+// launcher: in place on slices of the caller's arrays (the kernel reads coeffs and times as doubles and
+// writes whole mtg_extremum structs: 8-byte alignment is all a slice needs), or on packed copies of
+// the gathered groups' coefficients and times, whose results one kernel then moves to minimum[b] and
+// maximum[b].  Upload, gather, one launch per group in ascending K, scatter: one stream, no host
+// synchronisation in between.
+int run_min_max_ragged(mtg_ctx* ctx, int N, int D, const mtg::RaggedPlan& plan, const double* coeffs, const double* times,
+                       int derivative, uint32_t dims, mtg_extremum* minimum, mtg_extremum* maximum, unsigned flags) {
+  const size_t DN = (size_t)D * N;
+  const size_t nB = plan.vo.size() - 1, totS = (size_t)plan.total_segments();
+  const size_t nG = plan.members.size(), gS = (size_t)plan.pvo.back() - nG;
+  MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const double *d_coef, *d_times;
+  mtg_extremum *d_min, *d_max;
+  Staged st(ctx, flags);
+  st.in(&d_coef, coeffs, sizeof(double) * totS * DN);
+  st.in(&d_times, times, sizeof(double) * totS);
+  st.out(&d_min, minimum, sizeof(mtg_extremum) * nB);
+  st.out(&d_max, maximum, sizeof(mtg_extremum) * nB);
+  if (int rc = ragged_wait_last(ctx)) return rc;
+  if (int rc = st.upload()) return rc;
+  mtg::RaggedCoeffArgs ca{};
+  if (nG) {
+    size_t off = 0;
+    const size_t o_recs = off; off = align_up(off + sizeof(mtg::RaggedRec) * nG);
+    const size_t o_coef = off; off = align_up(off + sizeof(double) * gS * DN);
+    const size_t o_times = off; off = align_up(off + sizeof(double) * gS);
+    const size_t o_min = off; off = align_up(off + (d_min ? sizeof(mtg_extremum) * nG : 0));
+    const size_t o_max = off; off = align_up(off + (d_max ? sizeof(mtg_extremum) * nG : 0));
+    MTG_HIP_TRY(ctx, ensure(&ctx->ragged, &ctx->ragged_bytes, off));
+    char* base = static_cast<char*>(ctx->ragged);
+    if (int rc = ragged_upload_records(ctx, plan, base + o_recs)) return rc;
+    ca.recs = reinterpret_cast<const mtg::RaggedRec*>(base + o_recs);
+    ca.n = (int64_t)nG;
+    ca.DN = (int)DN;
+    ca.coeffs = d_coef;
+    ca.times = d_times;
+    ca.p_coeffs = reinterpret_cast<double*>(base + o_coef);
+    ca.p_times = reinterpret_cast<double*>(base + o_times);
+    ca.p_minimum = d_min ? reinterpret_cast<mtg_extremum*>(base + o_min) : nullptr;
+    ca.p_maximum = d_max ? reinterpret_cast<mtg_extremum*>(base + o_max) : nullptr;
+    ca.minimum = d_min;
+    ca.maximum = d_max;
+  }
+  MTG_HIP_TRY(ctx, time_begin(ctx, false));
+  if (nG) MTG_HIP_TRY(ctx, mtg::launch_ragged_gather_coeffs(ca, ctx->stream));
+  for (const mtg::RaggedGroup& g : plan.groups) {
+    // the group's arrays: slices of the CSR arrays at its first member, or of the packed arrays
+    const int64_t s0 = g.in_place ? plan.so(g.first) : plan.pso(g.first);
+    const double* gc = (g.in_place ? d_coef : ca.p_coeffs) + s0 * DN;
+    const double* gt = (g.in_place ? d_times : ca.p_times) + s0;
+    mtg_extremum* gmin = g.in_place ? d_min : ca.p_minimum;
+    mtg_extremum* gmax = g.in_place ? d_max : ca.p_maximum;
+    MTG_HIP_TRY(ctx, mtg::launch_min_max_magnitude(N, gc, gt, g.count, g.K, D, derivative, dims,
+                                                   gmin ? gmin + g.first : nullptr, gmax ? gmax + g.first : nullptr,
+                                                   ctx->stream));
+  }
+  if (nG) MTG_HIP_TRY(ctx, mtg::launch_ragged_scatter_extrema(ca, ctx->stream));
+  MTG_HIP_TRY(ctx, time_end(ctx));
+  if (nG)
+    if (int rc = ragged_mark_last(ctx)) return rc;
+  return st.finish();
+}
+
 // Body of mtg_solve_linear_ragged_batch: the gathered groups' inputs into packed
 // arrays (one kernel), one uniform solve launch per group in ascending K -- in place on slices of the
 // CSR arrays, or on the packed arrays -- and the gathered groups' outputs back (one kernel); all on
@@ -840,9 +1013,7 @@ int run_solve_ragged(mtg_ctx* ctx, int N, int D, int r, const mtg::RaggedPlan& p
   st.out(&d_nfree, n_free_out, sizeof(int32_t) * (size_t)batch);
   st.out(&d_cost, cost_out, sizeof(double) * (size_t)batch);
   st.out(&d_status, status, sizeof(int32_t) * (size_t)batch);
-  // an earlier ragged call may have run on another stream (mtg_set_stream): this call reuses its
-  // packed arrays and record buffer
-  if (ctx->ragged_done_pending) MTG_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ragged_done, 0));
+  if (int rc = ragged_wait_last(ctx)) return rc;
   if (int rc = st.upload()) return rc;
 
   // the DLX / split workspace, sized once for the largest group that needs it, before the first
@@ -873,31 +1044,7 @@ int run_solve_ragged(mtg_ctx* ctx, int N, int D, int r, const mtg::RaggedPlan& p
     const size_t o_status = off; off = align_up(off + (d_status ? sizeof(int32_t) * nG : 0));
     MTG_HIP_TRY(ctx, ensure(&ctx->ragged, &ctx->ragged_bytes, off));
     char* base = static_cast<char*>(ctx->ragged);
-    // the records, written into the pinned buffer whose turn it is once its last upload has landed
-    mtg_ctx::RaggedHost& hb = ctx->ragged_host[ctx->ragged_turn];
-    ctx->ragged_turn ^= 1;
-    if (!hb.uploaded) MTG_HIP_TRY(ctx, hipEventCreateWithFlags(&hb.uploaded, hipEventDisableTiming));
-    if (hb.pending) {
-      MTG_HIP_TRY(ctx, hipEventSynchronize(hb.uploaded));
-      hb.pending = false;
-    }
-    const size_t b_recs = sizeof(mtg::RaggedRec) * nG;
-    if (hb.bytes < b_recs) {
-      if (hb.p) MTG_HIP_TRY(ctx, hipHostFree(hb.p));
-      hb.p = nullptr;
-      hb.bytes = 0;
-      const size_t want = std::max<size_t>(b_recs + b_recs / 2, 4096);
-      MTG_HIP_TRY(ctx, hipHostMalloc(&hb.p, want, hipHostMallocDefault));
-      hb.bytes = want;
-    }
-    mtg::RaggedRec* recs = static_cast<mtg::RaggedRec*>(hb.p);
-    for (size_t j = 0; j < nG; ++j) {
-      const int64_t b = plan.members[j];
-      recs[j] = mtg::RaggedRec{plan.vo[(size_t)b], plan.pvo[j], b, (int32_t)(plan.vo[(size_t)b + 1] - plan.vo[(size_t)b] - 1), 0};
-    }
-    MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_recs, hb.p, b_recs, hipMemcpyHostToDevice, ctx->stream));
-    MTG_HIP_TRY(ctx, hipEventRecord(hb.uploaded, ctx->stream));
-    hb.pending = true;
+    if (int rc = ragged_upload_records(ctx, plan, base + o_recs)) return rc;
     ca.recs = reinterpret_cast<const mtg::RaggedRec*>(base + o_recs);
     ca.n = (int64_t)nG;
     ca.hD = (int)hD;
@@ -966,11 +1113,8 @@ int run_solve_ragged(mtg_ctx* ctx, int N, int D, int r, const mtg::RaggedPlan& p
   }
   if (nG) MTG_HIP_TRY(ctx, mtg::launch_ragged_scatter(ca, ctx->stream));
   MTG_HIP_TRY(ctx, time_end(ctx));
-  if (nG) {
-    if (!ctx->ragged_done) MTG_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ragged_done, hipEventDisableTiming));
-    MTG_HIP_TRY(ctx, hipEventRecord(ctx->ragged_done, ctx->stream));
-    ctx->ragged_done_pending = true;
-  }
+  if (nG)
+    if (int rc = ragged_mark_last(ctx)) return rc;
   return st.finish();
 }
 
@@ -1889,6 +2033,33 @@ int mtg_min_max_magnitude_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch
   return st.finish();
 }
 
+int mtg_min_max_magnitude_ragged_batch(mtg_ctx* ctx, int N, int D, int64_t batch, const int32_t* seg_count,
+                                       const double* coeffs, const double* times, int derivative,
+                                       uint32_t dimension_mask, mtg_extremum* minimum, mtg_extremum* maximum,
+                                       unsigned flags) {
+  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
+  if (int rc = check_order(ctx, N)) return rc;
+  if (D < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need D >= 1, batch >= 0");
+  if (derivative < 0 || derivative > N - 2)
+    return set_error(ctx, MTG_ERR_BAD_DERIVATIVE, "derivative must be in [0, N-2] (polynomial.cpp:62-65)");
+  const uint32_t all = D >= 32 ? 0xffffffffu : ((1u << D) - 1u);
+  const uint32_t dims = dimension_mask ? dimension_mask : all;
+  if (D > 32 || (dims & ~all)) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "dimension_mask out of range");
+  if (batch == 0) return MTG_OK;
+  if (!seg_count) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "seg_count is required (a host array)");
+  try {
+    mtg::RaggedPlan plan;
+    if (mtg::ragged_plan(batch, seg_count, &plan) != MTG_OK)
+      return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "every seg_count must be >= 1");
+    if (plan.groups.back().K > 256) return set_error(ctx, MTG_ERR_TOO_LARGE, "every seg_count must be <= 256");
+    if (!coeffs || !times) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "coeffs and times are required");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    return run_min_max_ragged(ctx, N, D, plan, coeffs, times, derivative, dims, minimum, maximum, flags);
+  } catch (const std::bad_alloc&) {
+    return set_error(ctx, MTG_ERR_OUT_OF_MEMORY, "ragged min / max magnitude: out of host memory");
+  }
+}
+
 int mtg_evaluate_at_path(int N, int D, int K, int64_t M, int n_derivatives) {
   if (int rc = check_order(nullptr, N)) return rc;
   if (int rc = check_dims(nullptr, D, K, M)) return rc;
@@ -1935,6 +2106,40 @@ int mtg_evaluate_at_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, cons
                                            n_derivatives, d_out, d_in, d_status, ctx->stream));
   MTG_HIP_TRY(ctx, time_end(ctx));
   return st.finish();
+}
+
+int mtg_evaluate_at_ragged_path(int N, int D, int K_max, int64_t M, int n_derivatives) {
+  return mtg_evaluate_at_path(N, D, K_max, M, n_derivatives);
+}
+
+int mtg_evaluate_at_ragged_batch(mtg_ctx* ctx, int N, int D, int64_t batch, const int32_t* seg_count,
+                                 const double* coeffs, const double* times, const double* t_query, int64_t t_stride,
+                                 int64_t M, int derivative_begin, int n_derivatives, double* out,
+                                 uint8_t* in_range_out, int32_t* status, unsigned flags) {
+  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
+  if (int rc = check_order(ctx, N)) return rc;
+  if (D < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need D >= 1, batch >= 0");
+  if (M < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need M >= 0");
+  if (derivative_begin < 0 || n_derivatives < 1 || n_derivatives > N)
+    return set_error(ctx, MTG_ERR_BAD_DERIVATIVE, "need derivative_begin >= 0 and n_derivatives in [1, N]");
+  if (t_stride < 0 || (t_stride > 0 && t_stride < M))
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "t_stride must be 0 (shared query times) or >= M");
+  int k_max = 0;
+  try {
+    std::vector<int64_t> so;
+    if (int rc = ragged_check_counts(ctx, batch, seg_count, &k_max, &so)) return rc;
+    mtg::EvalAtPlan plan;
+    if (!mtg::evaluate_at_plan(N, D, std::max(k_max, 1), M, n_derivatives, &plan))
+      return set_error(ctx, MTG_ERR_TOO_LARGE, "a block's rows exceed LDS (n_derivatives * D > 128)");
+    if (batch == 0 || M == 0) return MTG_OK;
+    if (!coeffs || !times || !t_query || !out)
+      return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "coeffs, times, t_query and out are required");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    return run_evaluate_at_ragged(ctx, N, D, k_max, so, coeffs, times, t_query, t_stride, M, derivative_begin,
+                                  n_derivatives, out, in_range_out, status, flags);
+  } catch (const std::bad_alloc&) {
+    return set_error(ctx, MTG_ERR_OUT_OF_MEMORY, "ragged evaluate: out of host memory");
+  }
 }
 
 int mtg_evaluate_range_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch,

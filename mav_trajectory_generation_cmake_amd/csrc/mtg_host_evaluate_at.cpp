@@ -8,6 +8,7 @@
 #include <cfloat>
 #include <cmath>
 #include <limits>
+#include <vector>
 
 #include "mtg.h"
 #include "mtg_host_threads.h"
@@ -93,6 +94,40 @@ extern "C" int mtg_host_evaluate_at_batch(int N, int D, int K, int64_t batch, co
     for (int64_t b = b0; b < b1; ++b) {
       const int st = one(N, D, K, coeffs + b * sc, times + b * K, t_query + b * t_stride, M, derivative_begin,
                          n_derivatives, base, out + b * so, in_range_out ? in_range_out + b * M : nullptr);
+      if (status) status[b] = st;
+    }
+  });
+  return MTG_OK;
+}
+
+// Host path of mtg_evaluate_at_ragged_batch: the same scalar code on each trajectory's blocks of the
+// CSR arrays, threaded over trajectories.
+extern "C" int mtg_host_evaluate_at_ragged_batch(int N, int D, int64_t batch, const int32_t* seg_count,
+                                                 const double* coeffs, const double* times, const double* t_query,
+                                                 int64_t t_stride, int64_t M, int derivative_begin, int n_derivatives,
+                                                 double* out, uint8_t* in_range_out, int32_t* status, int threads) {
+  if (N < 2 || N > 12 || (N % 2)) return MTG_ERR_UNSUPPORTED_N;
+  if (D < 1 || batch < 0 || M < 0) return MTG_ERR_SIZE_MISMATCH;
+  if (derivative_begin < 0 || n_derivatives < 1 || n_derivatives > N) return MTG_ERR_BAD_DERIVATIVE;
+  if (t_stride < 0 || (t_stride > 0 && t_stride < M)) return MTG_ERR_INVALID_ARGUMENT;
+  if (batch == 0) return MTG_OK;
+  if (!seg_count) return MTG_ERR_INVALID_ARGUMENT;
+  std::vector<int64_t> so((size_t)batch + 1, 0);
+  for (int64_t b = 0; b < batch; ++b) {
+    if (seg_count[b] < 1) return MTG_ERR_SIZE_MISMATCH;
+    so[(size_t)b + 1] = so[(size_t)b] + seg_count[b];
+  }
+  if (M == 0) return MTG_OK;
+  if (!coeffs || !times || !t_query || !out) return MTG_ERR_INVALID_ARGUMENT;
+  double base[12][12];
+  for (int k = 0; k < 12; ++k)
+    for (int j = 0; j < 12; ++j) base[k][j] = base_coeff(k, j);
+  const size_t DN = (size_t)D * N, row = (size_t)M * n_derivatives * D;
+  mtg::run_threads(batch, threads, [&](int64_t b0, int64_t b1) {
+    for (int64_t b = b0; b < b1; ++b) {
+      const size_t s0 = (size_t)so[(size_t)b];
+      const int st = one(N, D, seg_count[b], coeffs + s0 * DN, times + s0, t_query + b * t_stride, M, derivative_begin,
+                         n_derivatives, base, out + b * row, in_range_out ? in_range_out + b * M : nullptr);
       if (status) status[b] = st;
     }
   });

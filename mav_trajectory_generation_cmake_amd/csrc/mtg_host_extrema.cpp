@@ -56,3 +56,34 @@ extern "C" int mtg_host_min_max_magnitude_batch(int N, int D, int K, int64_t bat
   });
   return MTG_OK;
 }
+
+// Host path of mtg_min_max_magnitude_ragged_batch: the same scalar code on each trajectory's blocks of
+// the CSR arrays, threaded over trajectories.
+extern "C" int mtg_host_min_max_magnitude_ragged_batch(int N, int D, int64_t batch, const int32_t* seg_count,
+                                                       const double* coeffs, const double* times, int derivative,
+                                                       uint32_t dimension_mask, mtg_extremum* minimum,
+                                                       mtg_extremum* maximum, int threads) {
+  if (N < 2 || N > 12 || (N % 2)) return MTG_ERR_UNSUPPORTED_N;
+  if (D < 1 || batch < 0) return MTG_ERR_SIZE_MISMATCH;
+  if (derivative < 0 || derivative > N - 2) return MTG_ERR_BAD_DERIVATIVE;
+  const uint32_t all = D >= 32 ? 0xffffffffu : ((1u << D) - 1u);
+  const uint32_t dims = dimension_mask ? dimension_mask : all;
+  if (D > 32 || (dims & ~all)) return MTG_ERR_INVALID_ARGUMENT;
+  if (batch == 0) return MTG_OK;
+  if (!seg_count) return MTG_ERR_INVALID_ARGUMENT;
+  std::vector<int64_t> so((size_t)batch + 1, 0);
+  for (int64_t b = 0; b < batch; ++b) {
+    if (seg_count[b] < 1) return MTG_ERR_SIZE_MISMATCH;
+    so[(size_t)b + 1] = so[(size_t)b] + seg_count[b];
+  }
+  if (!coeffs || !times) return MTG_ERR_INVALID_ARGUMENT;
+  const size_t DN = (size_t)D * N;
+  mtg::run_threads(batch, threads, [&](int64_t b0, int64_t b1) {
+    for (int64_t b = b0; b < b1; ++b) {
+      const size_t s0 = (size_t)so[(size_t)b];
+      one(N, D, seg_count[b], coeffs + s0 * DN, times + s0, derivative, dims, minimum ? minimum + b : nullptr,
+          maximum ? maximum + b : nullptr);
+    }
+  });
+  return MTG_OK;
+}

@@ -107,6 +107,20 @@ struct RaggedCopyArgs {
 };
 hipError_t launch_ragged_gather(const RaggedCopyArgs& a, hipStream_t stream);
 hipError_t launch_ragged_scatter(const RaggedCopyArgs& a, hipStream_t stream);
+// The copy kernels of the ragged min / max magnitude, driven by the same records: coeffs and times of
+// the gathered trajectories into packed arrays (a wave per trajectory, as launch_ragged_gather), and
+// their extremes from the packed arrays to minimum[b] / maximum[b] (nullable pairs; a lane each).
+struct RaggedCoeffArgs {
+  const RaggedRec* recs;  // [n]
+  int64_t n;
+  int DN;                 // D N
+  const double *coeffs, *times;                 // the caller's CSR arrays
+  double *p_coeffs, *p_times;                   // the packed arrays
+  mtg_extremum *p_minimum, *p_maximum;          // [n] (the group launches write them, the scatter reads them)
+  mtg_extremum *minimum, *maximum;              // [B]
+};
+hipError_t launch_ragged_gather_coeffs(const RaggedCoeffArgs& a, hipStream_t stream);
+hipError_t launch_ragged_scatter_extrema(const RaggedCoeffArgs& a, hipStream_t stream);
 
 // cost / gradient of fixed vertex derivatives at candidate times (mtg_cost.hip)
 size_t cost_lds_bytes(int N, int D, int K);
@@ -242,6 +256,14 @@ bool evaluate_at_plan(int N, int D, int K, int64_t M, int n_derivatives, EvalAtP
 hipError_t launch_evaluate_at(int N, int D, int K, int64_t B, const double* coeffs, const double* times,
                               const double* t_query, int64_t t_stride, int64_t M, int derivative_begin,
                               int n_derivatives, double* out, uint8_t* in_range, int32_t* status, hipStream_t stream);
+
+// the same for a CSR batch (mtg_evaluate_at_ragged.hip): trajectory b's segments are
+// seg_off[b] .. seg_off[b + 1] of coeffs [sum K][D][N] and times [sum K]; seg_off [B + 1] is a device
+// array; the plan is evaluate_at_plan at K_max, the largest segment count of the batch
+hipError_t launch_evaluate_at_ragged(int N, int D, int K_max, int64_t B, const int64_t* seg_off, const double* coeffs,
+                                     const double* times, const double* t_query, int64_t t_stride, int64_t M,
+                                     int derivative_begin, int n_derivatives, double* out, uint8_t* in_range,
+                                     int32_t* status, hipStream_t stream);
 
 // evaluateRange
 hipError_t launch_eval_count(int N, int D, int K, int64_t B, const double* times, double t_start,

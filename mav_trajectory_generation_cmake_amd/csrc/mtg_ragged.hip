@@ -1,12 +1,17 @@
-// mtg_ragged.hip -- the two copy kernels of the ragged solve (mtg_solve_linear_ragged_batch,
-// DESIGN.md 3.14).  A ragged batch keeps trajectories of different segment counts K in CSR arrays;
+// mtg_ragged.hip -- the copy kernels of the ragged entries: the two of the ragged solve
+// (mtg_solve_linear_ragged_batch) and the two of the ragged min / max magnitude
+// (mtg_min_max_magnitude_ragged_batch).  A ragged batch keeps trajectories of different segment counts K in CSR arrays;
 // the groups whose members are not consecutive are gathered into packed uniform arrays, solved by the
 // existing kernels, and scattered back:
 //
 // * ragged_gather_kernel: values, fixed_mask and times of every gathered trajectory, from the caller's
 //   CSR arrays into the packed arrays;
 // * ragged_scatter_kernel: coeffs, free_out, n_free_out, cost_out and status (those requested) of
-//   every gathered trajectory, from the packed arrays to their CSR positions.
+//   every gathered trajectory, from the packed arrays to their CSR positions;
+// * ragged_gather_coeffs_kernel: coeffs and times of every gathered trajectory into packed arrays, for
+//   the entries that consume solved coefficients;
+// * ragged_scatter_extrema_kernel: the gathered trajectories' minimum and maximum to minimum[b] and
+//   maximum[b] (a lane per trajectory: one 24-byte struct each).
 //
 // One launch each for all gathered groups, driven by one record per gathered trajectory (RaggedRec).
 // A wave owns a trajectory and its lanes stride over the trajectory's doubles, so a wave instruction
@@ -97,9 +102,28 @@ __global__ __launch_bounds__(kRaggedThreads) void ragged_scatter_kernel(RaggedCo
   if (a.coeffs) wave_copy<4>(a.p_coeffs + dst_s * a.DN, a.coeffs + src_s * a.DN, K * a.DN, lane);
 }
 
-hipError_t launch_copy(void (*kernel)(RaggedCopyArgs), const RaggedCopyArgs& a, hipStream_t stream) {
+__global__ __launch_bounds__(kRaggedThreads) void ragged_gather_coeffs_kernel(RaggedCoeffArgs a) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t j = (int64_t)blockIdx.x * (kRaggedThreads / kWave) + (threadIdx.x >> 6);
+  if (j >= a.n) return;
+  const RaggedRec rec = a.recs[j];
+  const int K = rec.K;
+  const int64_t src_s = rec.src_v - rec.b, dst_s = rec.dst_v - j;
+  wave_copy<1>(a.times + src_s, a.p_times + dst_s, K, lane);
+  wave_copy<4>(a.coeffs + src_s * a.DN, a.p_coeffs + dst_s * a.DN, K * a.DN, lane);
+}
+
+__global__ __launch_bounds__(kRaggedThreads) void ragged_scatter_extrema_kernel(RaggedCoeffArgs a) {
+  const int64_t j = (int64_t)blockIdx.x * kRaggedThreads + threadIdx.x;
+  if (j >= a.n) return;
+  const int64_t b = a.recs[j].b;
+  if (a.minimum) a.minimum[b] = a.p_minimum[j];
+  if (a.maximum) a.maximum[b] = a.p_maximum[j];
+}
+
+template <class Args>
+hipError_t launch_copy(void (*kernel)(Args), const Args& a, hipStream_t stream, int per = kRaggedThreads / kWave) {
   if (a.n <= 0) return hipSuccess;
-  const int per = kRaggedThreads / kWave;
   const int64_t blocks = (a.n + per - 1) / per;
   if (blocks > 0x7fffffff) return hipErrorInvalidValue;
   launch_kernel(kernel, dim3((unsigned)blocks), dim3(kRaggedThreads), 0, stream, a);
@@ -114,6 +138,14 @@ hipError_t launch_ragged_gather(const RaggedCopyArgs& a, hipStream_t stream) {
 
 hipError_t launch_ragged_scatter(const RaggedCopyArgs& a, hipStream_t stream) {
   return launch_copy(ragged_scatter_kernel, a, stream);
+}
+
+hipError_t launch_ragged_gather_coeffs(const RaggedCoeffArgs& a, hipStream_t stream) {
+  return launch_copy(ragged_gather_coeffs_kernel, a, stream);
+}
+
+hipError_t launch_ragged_scatter_extrema(const RaggedCoeffArgs& a, hipStream_t stream) {
+  return launch_copy(ragged_scatter_extrema_kernel, a, stream, kRaggedThreads);
 }
 
 }  // namespace mtg

@@ -694,6 +694,102 @@ class Context:
                                                   _addr(in_range), _addr(status), flags), self.handle)
         return out, in_range, status
 
+    # --------------------------------------------- ragged K, after the solve
+    def evaluate_at_ragged_batch(self, coeffs, times, seg_count, t_query, derivative_begin=0, n_derivatives=1,
+                                 want_in_range=True, asynchronous=False):
+        """evaluate_at_batch for a batch of different segment counts (mtg_evaluate_at_ragged_batch): coeffs
+        [sum K][D][N] and times [sum K] are the CSR arrays Context.solve_linear_ragged_batch returns and takes
+        (numpy or torch-device), seg_count [B] a host array either way; t_query, the other arguments and the
+        result are those of evaluate_at_batch.  Every trajectory's rows are the bytes evaluate_at_batch gives
+        for it alone.  coeffs and times may also be lists of per-trajectory blocks (split_ragged): joined first."""
+        coeffs, times = _csr(coeffs), _csr(times)
+        dev = _is_torch(coeffs) and coeffs.is_cuda
+        seg_count, B, D, N = _ragged_coeff_shape(coeffs, times, seg_count)
+        if dev:
+            import torch
+            kw = dict(device=coeffs.device)
+            coeffs, times = coeffs.contiguous(), times.contiguous()
+            t_query, t_stride, M = _query_rows(t_query, B, lambda a: a.stride(), lambda a: a.contiguous())
+            out = torch.empty((B, M, n_derivatives, D), dtype=torch.float64, **kw)
+            in_range = torch.empty((B, M), dtype=torch.uint8, **kw) if want_in_range else None
+            status = torch.empty(B, dtype=torch.int32, **kw)
+            flags = nat.MTG_FLAG_DEVICE_PTRS | (nat.MTG_FLAG_ASYNC if asynchronous else 0)
+            self.set_stream(torch.cuda.current_stream(coeffs.device).cuda_stream)
+        else:
+            coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+            times = np.ascontiguousarray(times, dtype=np.float64)
+            t_query, t_stride, M = _query_rows_numpy(t_query, B)
+            out = np.empty((B, M, n_derivatives, D))
+            in_range = np.empty((B, M), np.uint8) if want_in_range else None
+            status = np.empty(B, np.int32)
+            flags = 0
+            self.reset_stream()
+        nat.check(self._lib.mtg_evaluate_at_ragged_batch(self.handle, N, D, B, _addr(seg_count), _addr(coeffs),
+                                                         _addr(times), _addr(t_query), t_stride, M,
+                                                         int(derivative_begin), int(n_derivatives), _addr(out),
+                                                         _addr(in_range), _addr(status), flags), self.handle)
+        return out, in_range, status
+
+    def min_max_magnitude_ragged_batch(self, coeffs, times, seg_count, derivative, dimensions=None, minimum=True,
+                                       maximum=True, asynchronous=False):
+        """min_max_magnitude_batch for a batch of different segment counts
+        (mtg_min_max_magnitude_ragged_batch): coeffs [sum K][D][N], times [sum K] (numpy or torch-device) and
+        the host array seg_count [B].  Returns (minimum, maximum), each a structured array [B]
+        (EXTREMUM_DTYPE; for device arrays a torch uint8 tensor [B][24] on the device, see extrema_from_bytes)
+        or None where minimum=False / maximum=False.  Every entry is the bytes min_max_magnitude_batch gives
+        for that trajectory alone.  coeffs and times may also be lists of per-trajectory blocks (split_ragged)."""
+        coeffs, times = _csr(coeffs), _csr(times)
+        dev = _is_torch(coeffs) and coeffs.is_cuda
+        seg_count, B, D, N = _ragged_coeff_shape(coeffs, times, seg_count)
+        mask = 0 if dimensions is None else int(sum(1 << int(d) for d in dimensions))
+        if dev:
+            import torch
+            coeffs, times = coeffs.contiguous(), times.contiguous()
+            mn, mx = (torch.zeros((B, EXTREMUM_DTYPE.itemsize), dtype=torch.uint8, device=coeffs.device) if want else None
+                      for want in (minimum, maximum))
+            flags = nat.MTG_FLAG_DEVICE_PTRS | (nat.MTG_FLAG_ASYNC if asynchronous else 0)
+            self.set_stream(torch.cuda.current_stream(coeffs.device).cuda_stream)
+        else:
+            coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+            times = np.ascontiguousarray(times, dtype=np.float64)
+            mn, mx = (np.zeros(B, dtype=EXTREMUM_DTYPE) if want else None for want in (minimum, maximum))
+            flags = 0
+            self.reset_stream()
+        nat.check(self._lib.mtg_min_max_magnitude_ragged_batch(self.handle, N, D, B, _addr(seg_count), _addr(coeffs),
+                                                               _addr(times), int(derivative), mask, _addr(mn),
+                                                               _addr(mx), flags), self.handle)
+        return mn, mx
+
+
+def extrema_from_bytes(t):
+    """The structured array [B] (EXTREMUM_DTYPE) of a device result of min_max_magnitude_ragged_batch (a torch
+    uint8 tensor [B][24]); waits for the tensor's stream."""
+    return np.ascontiguousarray(t.cpu().numpy()).view(EXTREMUM_DTYPE).reshape(-1)
+
+
+def join_ragged(per_trajectory):
+    """One CSR array of per-trajectory blocks (what split_ragged yields: coeffs [K_b][D][N] or times [K_b]),
+    numpy or torch; a copy."""
+    per_trajectory = list(per_trajectory)
+    if per_trajectory and _is_torch(per_trajectory[0]):
+        import torch
+        return torch.cat(per_trajectory)
+    return np.concatenate([np.asarray(x, dtype=np.float64) for x in per_trajectory])
+
+
+def _csr(x):
+    """A CSR array as it is; a list of per-trajectory blocks (split_ragged) joined."""
+    return join_ragged(x) if isinstance(x, (list, tuple)) else x
+
+
+def _ragged_coeff_shape(coeffs, times, seg_count):
+    """(seg_count as int32, B, D, N) of the CSR arrays coeffs [sum K][D][N], times [sum K]."""
+    seg_count = np.ascontiguousarray(seg_count, dtype=np.int32).reshape(-1)
+    totS = int(seg_count.sum(dtype=np.int64))
+    assert coeffs.ndim == 3 and int(coeffs.shape[0]) == totS, "coeffs must be [sum K][D][N]"
+    assert tuple(times.shape) == (totS,), "times must be [sum K]"
+    return seg_count, int(seg_count.shape[0]), int(coeffs.shape[1]), int(coeffs.shape[2])
+
 
 def _query_rows(t_query, B, strides, contiguous):
     """(array, t_stride, M) of evaluate_at's query times: [M] is shared (stride 0); [B][M] keeps its row
@@ -1377,6 +1473,41 @@ def host_solve_linear_ragged_batch(N, r, values, mask, times, seg_count, free=Fa
                                                      _addr(out.get("n_free")), _addr(out.get("cost")),
                                                      _addr(out.get("status")), threads))
     return out
+
+
+def host_evaluate_at_ragged_batch(coeffs, times, seg_count, t_query, derivative_begin=0, n_derivatives=1,
+                                  want_in_range=True, threads=0):
+    """Context.evaluate_at_ragged_batch on the library's host path (mtg_host_evaluate_at_ragged_batch): no GPU;
+    every trajectory's rows are the bytes host_evaluate_at_batch gives for it alone.  numpy CSR arrays (or lists
+    of per-trajectory blocks, as split_ragged yields); threads <= 0: mtg_host_default_threads()."""
+    coeffs = np.ascontiguousarray(_csr(coeffs), dtype=np.float64)
+    times = np.ascontiguousarray(_csr(times), dtype=np.float64)
+    seg_count, B, D, N = _ragged_coeff_shape(coeffs, times, seg_count)
+    t_query, t_stride, M = _query_rows_numpy(t_query, B)
+    out = np.empty((B, M, n_derivatives, D))
+    in_range = np.empty((B, M), np.uint8) if want_in_range else None
+    status = np.empty(B, np.int32)
+    nat.check(nat.load().mtg_host_evaluate_at_ragged_batch(N, D, B, _addr(seg_count), _addr(coeffs), _addr(times),
+                                                           _addr(t_query), t_stride, M, int(derivative_begin),
+                                                           int(n_derivatives), _addr(out), _addr(in_range),
+                                                           _addr(status), int(threads)))
+    return out, in_range, status
+
+
+def host_min_max_magnitude_ragged_batch(coeffs, times, seg_count, derivative, dimensions=None, threads=1):
+    """Context.min_max_magnitude_ragged_batch on the library's host path
+    (mtg_host_min_max_magnitude_ragged_batch): no GPU; every entry is the bytes host_min_max_magnitude_batch
+    gives for that trajectory alone.  numpy CSR arrays (or lists of per-trajectory blocks)."""
+    coeffs = np.ascontiguousarray(_csr(coeffs), dtype=np.float64)
+    times = np.ascontiguousarray(_csr(times), dtype=np.float64)
+    seg_count, B, D, N = _ragged_coeff_shape(coeffs, times, seg_count)
+    mask = 0 if dimensions is None else int(sum(1 << int(d) for d in dimensions))
+    mn = np.zeros(B, dtype=EXTREMUM_DTYPE)
+    mx = np.zeros(B, dtype=EXTREMUM_DTYPE)
+    nat.check(nat.load().mtg_host_min_max_magnitude_ragged_batch(N, D, B, _addr(seg_count), _addr(coeffs), _addr(times),
+                                                                 int(derivative), mask, _addr(mn), _addr(mx),
+                                                                 int(threads)))
+    return mn, mx
 
 
 # ----------------------------------------------------------------- generators
