@@ -480,6 +480,48 @@ inline void evaluateAt(int D, int K, int64_t batch, const double* coeffs, const 
   }
 }
 
+// Per-segment extrema on a window with the candidate list (mtg_segment_min_max_magnitude_batch,
+// mtg_segment_min_max_axis_batch), without a BatchPolynomialOptimization object: coeffs
+// [n_segments][D][N] and times [n_segments] carry no trajectory structure, so a uniform batch and the
+// CSR arrays of a ragged one are both valid.  On the library's host paths unless the execution policy
+// is kDevice, as evaluateAt.  Host pointers; every output is nullable.
+template <int N>
+inline void segmentMinMaxMagnitude(int D, int64_t n_segments, const double* coeffs, const double* times,
+                                   const double* windows, int derivative, uint32_t dimension_mask,
+                                   mtg_extremum* minimum, mtg_extremum* maximum, double* candidate_times = nullptr,
+                                   int32_t* candidate_count = nullptr, int candidate_capacity = 0,
+                                   int32_t* status = nullptr) {
+  if (singleOnDevice()) {
+    mtg_ctx* ctx = defaultContext();
+    check(mtg_segment_min_max_magnitude_batch(ctx, N, D, n_segments, coeffs, times, windows, derivative, dimension_mask,
+                                              minimum, maximum, candidate_times, candidate_count, candidate_capacity,
+                                              status, 0),
+          ctx, "mtg_segment_min_max_magnitude_batch");
+  } else {
+    check(mtg_host_segment_min_max_magnitude_batch(N, D, n_segments, coeffs, times, windows, derivative, dimension_mask,
+                                                   minimum, maximum, candidate_times, candidate_count,
+                                                   candidate_capacity, status, 1),
+          nullptr, "mtg_host_segment_min_max_magnitude_batch");
+  }
+}
+
+template <int N>
+inline void segmentMinMaxAxis(int D, int64_t n_segments, const double* coeffs, const double* times,
+                              const double* windows, int derivative, mtg_extremum* minimum, mtg_extremum* maximum,
+                              double* candidate_times = nullptr, int32_t* candidate_count = nullptr,
+                              int candidate_capacity = 0, int32_t* status = nullptr) {
+  if (singleOnDevice()) {
+    mtg_ctx* ctx = defaultContext();
+    check(mtg_segment_min_max_axis_batch(ctx, N, D, n_segments, coeffs, times, windows, derivative, minimum, maximum,
+                                         candidate_times, candidate_count, candidate_capacity, status, 0),
+          ctx, "mtg_segment_min_max_axis_batch");
+  } else {
+    check(mtg_host_segment_min_max_axis_batch(N, D, n_segments, coeffs, times, windows, derivative, minimum, maximum,
+                                              candidate_times, candidate_count, candidate_capacity, status, 1),
+          nullptr, "mtg_host_segment_min_max_axis_batch");
+  }
+}
+
 // evaluateAt<N> and Trajectory::computeMinMaxMagnitude for trajectories of different segment counts in
 // the CSR layout (coeffs [sum K][D][N], times [sum K], seg_count [batch]), without a
 // BatchPolynomialOptimization object: on the library's host paths unless the execution policy is

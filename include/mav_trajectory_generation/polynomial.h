@@ -4,15 +4,17 @@
 // reference's Horner on base_coefficients_(d, j) c_j, multiply then add (the library is built with
 // -ffp-contract=off, and so must callers that want its last bits).
 //
-// Not provided: computeRoots / computeMinMax* / selectMinMax* (Jenkins-Traub root finding,
-// src/rpoly.cpp, outside the ported path): extrema of whole trajectories go through
-// Trajectory::computeMinMaxMagnitude (host or GPU, ExecutionPolicy).
+// computeMinMaxCandidates / computeMinMax / selectMinMaxFromCandidates run on the library's host
+// search (mtg_host_segment_min_max_axis_batch).  Not provided: computeRoots and the ...FromRoots
+// overloads, which take the complex roots of Jenkins-Traub (src/rpoly.cpp, outside the ported path).
 #ifndef MAV_TRAJECTORY_GENERATION_POLYNOMIAL_H_
 #define MAV_TRAJECTORY_GENERATION_POLYNOMIAL_H_
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <limits>
+#include <utility>
 #include <vector>
 
 #include "mav_trajectory_generation/linalg.h"
@@ -105,6 +107,55 @@ class Polynomial {
     return result;
   }
 
+  // Candidates for the extremes of the derivative-th derivative on [t_start, t_end]: t_start, t_end,
+  // then the real roots of the (derivative + 1)-th derivative in the window, ascending
+  // (src/polynomial.cpp:57-78 over :27-55).  The roots come from the library's host search
+  // (mtg_host_segment_min_max_axis_batch: 256 samples on the window, safeguarded Newton), not from
+  // Jenkins-Traub.  false: N - derivative - 1 < 0, t_start > t_end or a window that is not finite.  A
+  // zero polynomial has no roots (rpoly.cpp:62-65): the two ends, true.  N <= 12 and derivative >= 0.
+  bool computeMinMaxCandidates(double t_start, double t_end, int derivative, std::vector<double>* candidates) const {
+    check_notnull(candidates, "candidates");
+    candidates->clear();
+    if (N_ - derivative - 1 < 0) {
+      warn("N - derivative - 1 has to be at least 0.");
+      return false;
+    }
+    return searchWindow(t_start, t_end, derivative, candidates, nullptr, nullptr);
+  }
+
+  // Minimum and maximum, as pair<t, value>, of the derivative-th derivative on [t_start, t_end]
+  // (src/polynomial.cpp:97-109): the first candidate wins ties.
+  bool computeMinMax(double t_start, double t_end, int derivative, std::pair<double, double>* minimum,
+                     std::pair<double, double>* maximum) const {
+    check_notnull(minimum, "minimum");
+    check_notnull(maximum, "maximum");
+    if (N_ - derivative - 1 < 0) {
+      warn("N - derivative - 1 has to be at least 0.");
+      return false;
+    }
+    return searchWindow(t_start, t_end, derivative, nullptr, minimum, maximum);
+  }
+
+  // The same among given candidate times (src/polynomial.cpp:111-138): strict comparisons, so the first
+  // candidate wins ties; false for an empty set.
+  bool selectMinMaxFromCandidates(const std::vector<double>& candidates, int derivative,
+                                  std::pair<double, double>* minimum, std::pair<double, double>* maximum) const {
+    check_notnull(minimum, "minimum");
+    check_notnull(maximum, "maximum");
+    if (candidates.empty()) {
+      warn("Cannot find extrema from an empty candidates vector.");
+      return false;
+    }
+    *minimum = std::make_pair(candidates[0], std::numeric_limits<double>::max());
+    *maximum = std::make_pair(candidates[0], std::numeric_limits<double>::lowest());
+    for (double t : candidates) {
+      const double value = evaluate(t, derivative);
+      if (value < minimum->second) *minimum = std::make_pair(t, value);
+      if (value > maximum->second) *maximum = std::make_pair(t, value);
+    }
+    return true;
+  }
+
   // Row `derivative` of A(t): B(derivative, j) t^(j - derivative); only the j == derivative entry
   // when |t| < epsilon (polynomial.h:215-243).
   static void baseCoeffsWithTime(int N, int derivative, double t, VectorXd* coeffs) {
@@ -137,6 +188,34 @@ class Polynomial {
   static int getConvolutionLength(int data_size, int kernel_size) { return data_size + kernel_size - 1; }
 
  private:
+  // One (segment, dimension) item of the host axis entry on [t_start, t_end].  The entry takes even
+  // N in 2..12 and derivative <= N - 2: the coefficients are padded with leading zeros to the smallest
+  // such N (the polynomial, its derivatives and their Horner values are unchanged).
+  bool searchWindow(double t_start, double t_end, int derivative, std::vector<double>* candidates,
+                    std::pair<double, double>* minimum, std::pair<double, double>* maximum) const {
+    int n = std::max(N_, derivative + 2);
+    n += n % 2;
+    if (derivative < 0 || n > kMaxN) fail(MTG_ERR_UNSUPPORTED_N, "computeMinMax*: need derivative >= 0 and N <= 12");
+    std::vector<double> c((size_t)n, 0.0);
+    for (int j = 0; j < N_; ++j) c[(size_t)j] = coefficients_[j];
+    const double window[2] = {t_start, t_end};
+    constexpr int kCap = 2 + 257;  // the ends, and at most one root per sample interval plus one at t_start
+    double times[kCap];
+    int32_t count = 0, status = 0;
+    mtg_extremum mn, mx;
+    check(mtg_host_segment_min_max_axis_batch(n, 1, 1, c.data(), nullptr, window, derivative, &mn, &mx, times, &count,
+                                              kCap, &status, 1),
+          nullptr, "mtg_host_segment_min_max_axis_batch");
+    if (status != MTG_TRAJ_OK) {
+      warn(t_start > t_end ? "t_start is greater than t_end." : "the window is not finite.");
+      return false;
+    }
+    if (candidates) candidates->assign(times, times + std::min<int>(count, kCap));
+    if (minimum) *minimum = std::make_pair(mn.time, mn.value);
+    if (maximum) *maximum = std::make_pair(mx.time, mx.value);
+    return true;
+  }
+
   int N_;
   VectorXd coefficients_;
 };

@@ -57,7 +57,9 @@ extern "C" {
                                     mtg_solve_ragged_plan
                                5, additive: + mtg_evaluate_at_ragged_batch, mtg_evaluate_at_ragged_path,
                                     mtg_host_evaluate_at_ragged_batch, mtg_min_max_magnitude_ragged_batch,
-                                    mtg_host_min_max_magnitude_ragged_batch */
+                                    mtg_host_min_max_magnitude_ragged_batch
+                               5, additive: + mtg_segment_min_max_magnitude_batch, mtg_segment_min_max_axis_batch,
+                                    mtg_host_segment_min_max_magnitude_batch, mtg_host_segment_min_max_axis_batch */
 
 /* Call-level return codes. */
 #define MTG_OK 0
@@ -448,6 +450,60 @@ int mtg_min_max_magnitude_ragged_batch(mtg_ctx* ctx, int N, int D, int64_t batch
                                        const double* coeffs, const double* times, int derivative,
                                        uint32_t dimension_mask, mtg_extremum* minimum, mtg_extremum* maximum,
                                        unsigned flags);
+
+/* Per-segment extrema on a time window, with the candidate list: the layer under
+ * Trajectory::computeMinMaxMagnitude.  A call has no trajectory structure -- coeffs [S][D][N],
+ * times [S] -- so a uniform batch (S = B K) and a CSR-packed ragged batch (S = sum K_b) are the same
+ * call: no plan, no gather, no indirection.  A segment's outputs depend only on that segment's inputs,
+ * not on S or on its index.
+ *
+ * mtg_segment_min_max_magnitude_batch: Segment::computeMinMaxMagnitudeCandidates followed by
+ * selectMinMaxMagnitudeFromCandidates (src/segment.cpp:82-196) on [t_start, t_end].  The candidates
+ * are t_start, t_end, then the real roots in the window of sum_{d in mask} conv(p_d^(k), p_d^(k+1))
+ * (one selected dimension: of p^(k+1)); the quantity is sqrt(sum_d p_d^(k)(t)^2); the first candidate
+ * in that order wins ties (std::max / std::min keep their first argument, segment.cpp:177-194).
+ * minimum / maximum [S], candidate_times [S][candidate_capacity], candidate_count [S].
+ *
+ * mtg_segment_min_max_axis_batch: Polynomial::computeMinMax (src/polynomial.cpp:97-138) for every
+ * (segment, dimension): the candidates are t_start, t_end and the real roots in the window of
+ * p_d^(k+1); the quantity is the SIGNED p_d^(k)(t); the comparisons are strict, so the first candidate
+ * wins ties (polynomial.cpp:126-136).  minimum / maximum [S][D], candidate_times
+ * [S][D][candidate_capacity], candidate_count [S][D].
+ *
+ * Common to both:
+ *   windows [S][2] = t_start, t_end, segment-local; NULL: [0, times[s]] (times may be NULL when windows
+ *     is given: it is not read).  The window is not clamped to [0, T]; the reference does not clamp it.
+ *   mtg_extremum.time is segment-local; .segment is 0, as Extremum(t, v, 0) leaves it.
+ *   Roots: the project's search, not Jenkins-Traub -- sign changes (and exact zeros) of the root
+ *     polynomial on the 257 samples t_start + s h, h = (t_end - t_start) / 256, the last sample t_end
+ *     itself, each bracket refined by the safeguarded Newton-bisection.  A root pair closer than h with
+ *     no sign change between samples is not isolated.  On [0, T] the per-segment
+ *     extremes are the values mtg_min_max_magnitude_batch reduces over a trajectory, bit for bit.
+ *   candidate_times lists t_start, t_end, then the isolated roots in ascending order; a root that
+ *     coincides with an end is listed as well.  candidate_count is the true count also when it exceeds
+ *     candidate_capacity; only the first candidate_capacity times are written and the rest of a row is
+ *     +0.0.  When every coefficient of the root polynomial is exactly zero (an axis held constant) the
+ *     list is the two ends and the count 2 (the reference's root finder returns no roots for the zero
+ *     polynomial, rpoly.cpp:62-65), while the min / max search stays the shared code's, which sees a
+ *     zero at every sample.
+ *   status [S]: MTG_TRAJ_BAD_TIME when the window is not finite, when t_start > t_end (the reference
+ *     returns false), or when there is no window and times[s] is not positive and finite.  Every floating
+ *     output of such a segment is NaN (its candidate rows included) and its counts are 0.
+ *   Every output pointer is nullable, and requesting one output never changes the bits of another.
+ * Errors: N, D, derivative (0 .. N-2) and dimension_mask (0 = all; a bit >= D: MTG_ERR_INVALID_ARGUMENT)
+ * as in mtg_min_max_magnitude_batch; MTG_ERR_SIZE_MISMATCH for n_segments < 0;
+ * MTG_ERR_INVALID_ARGUMENT for candidate_times with candidate_capacity < 2 and for a NULL ctx, coeffs,
+ * or times and windows both NULL with n_segments > 0.  n_segments == 0: MTG_OK.  MTG_FLAG_DEVICE_PTRS
+ * and MTG_FLAG_ASYNC as in the collision entries; a host-pointer call stages its arrays once. */
+int mtg_segment_min_max_magnitude_batch(mtg_ctx* ctx, int N, int D, int64_t n_segments, const double* coeffs,
+                                        const double* times, const double* windows, int derivative,
+                                        uint32_t dimension_mask, mtg_extremum* minimum, mtg_extremum* maximum,
+                                        double* candidate_times, int32_t* candidate_count, int candidate_capacity,
+                                        int32_t* status, unsigned flags);
+int mtg_segment_min_max_axis_batch(mtg_ctx* ctx, int N, int D, int64_t n_segments, const double* coeffs,
+                                   const double* times, const double* windows, int derivative, mtg_extremum* minimum,
+                                   mtg_extremum* maximum, double* candidate_times, int32_t* candidate_count,
+                                   int candidate_capacity, int32_t* status, unsigned flags);
 
 /* ---- Collision term of the nonlinear objective (kOptimizeFreeConstraintsAndCollision[AndTime]).
  *
@@ -999,6 +1055,22 @@ int mtg_host_min_max_magnitude_ragged_batch(int N, int D, int64_t batch, const i
                                             const double* coeffs, const double* times, int derivative,
                                             uint32_t dimension_mask, mtg_extremum* minimum, mtg_extremum* maximum,
                                             int threads);
+
+/* Host (CPU) paths of mtg_segment_min_max_magnitude_batch and mtg_segment_min_max_axis_batch, no
+ * context and no GPU needed: the same samples, refinement, candidate order and tie rules in scalar
+ * code (the search mtg_host_min_max_magnitude_batch runs per segment, on the window), threaded over
+ * segments.  The C++ drop-in's Polynomial::computeMinMax* and Segment::computeMinMaxMagnitude* use
+ * them.  All host pointers; the argument errors of the device calls; threads <= 0:
+ * mtg_host_default_threads(). */
+int mtg_host_segment_min_max_magnitude_batch(int N, int D, int64_t n_segments, const double* coeffs,
+                                             const double* times, const double* windows, int derivative,
+                                             uint32_t dimension_mask, mtg_extremum* minimum, mtg_extremum* maximum,
+                                             double* candidate_times, int32_t* candidate_count,
+                                             int candidate_capacity, int32_t* status, int threads);
+int mtg_host_segment_min_max_axis_batch(int N, int D, int64_t n_segments, const double* coeffs, const double* times,
+                                        const double* windows, int derivative, mtg_extremum* minimum,
+                                        mtg_extremum* maximum, double* candidate_times, int32_t* candidate_count,
+                                        int candidate_capacity, int32_t* status, int threads);
 
 /* ---- Host utilities (no GPU): the reference's synthetic-input generators,
  * bit-exact with libstdc++ <random>, packed straight into the ABI layout.

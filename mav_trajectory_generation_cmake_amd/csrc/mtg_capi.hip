@@ -2060,6 +2060,70 @@ int mtg_min_max_magnitude_ragged_batch(mtg_ctx* ctx, int N, int D, int64_t batch
   }
 }
 
+namespace {
+
+// Body of mtg_segment_min_max_magnitude_batch / mtg_segment_min_max_axis_batch: one launch over the
+// items (segments, or (segment, dimension) pairs), nothing else.
+int run_segment_extrema(mtg_ctx* ctx, bool axis, int N, int D, int64_t S, const double* coeffs, const double* times,
+                        const double* windows, int derivative, uint32_t dimension_mask, mtg_extremum* minimum,
+                        mtg_extremum* maximum, double* candidate_times, int32_t* candidate_count,
+                        int candidate_capacity, int32_t* status, unsigned flags) {
+  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
+  if (int rc = check_order(ctx, N)) return rc;
+  if (int rc = check_dims(ctx, D, 1, S)) return rc;
+  if (derivative < 0 || derivative > N - 2)
+    return set_error(ctx, MTG_ERR_BAD_DERIVATIVE, "derivative must be in [0, N-2] (polynomial.cpp:62-65)");
+  const uint32_t all = D >= 32 ? 0xffffffffu : ((1u << D) - 1u);
+  const uint32_t dims = dimension_mask ? dimension_mask : all;
+  if (D > 32 || (dims & ~all)) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "dimension_mask out of range");
+  if (candidate_times && candidate_capacity < 2)
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "candidate_capacity must be >= 2 (the two ends)");
+  if (S == 0) return MTG_OK;
+  if (!coeffs || (!times && !windows))
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "coeffs and times (or windows) are required");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t nS = (size_t)S, nI = axis ? nS * D : nS, cap = candidate_times ? (size_t)candidate_capacity : 0;
+  const double *d_coef, *d_times, *d_win;
+  mtg_extremum *d_min, *d_max;
+  double* d_cand;
+  int32_t *d_count, *d_status;
+  Staged st(ctx, flags);
+  st.in(&d_coef, coeffs, sizeof(double) * nS * D * N);
+  st.in(&d_times, times, sizeof(double) * nS);
+  st.in(&d_win, windows, sizeof(double) * nS * 2);
+  st.out(&d_min, minimum, sizeof(mtg_extremum) * nI);
+  st.out(&d_max, maximum, sizeof(mtg_extremum) * nI);
+  st.out(&d_cand, candidate_times, sizeof(double) * nI * cap);
+  st.out(&d_count, candidate_count, sizeof(int32_t) * nI);
+  st.out(&d_status, status, sizeof(int32_t) * nS);
+  if (int rc = st.upload()) return rc;
+  MTG_HIP_TRY(ctx, time_begin(ctx));
+  MTG_HIP_TRY(ctx, mtg::launch_segment_extrema(axis, N, d_coef, d_times, d_win, S, D, derivative, dims, d_min, d_max,
+                                               d_cand, d_count, candidate_capacity, d_status, ctx->stream));
+  MTG_HIP_TRY(ctx, time_end(ctx));
+  return st.finish();
+}
+
+}  // namespace
+
+int mtg_segment_min_max_magnitude_batch(mtg_ctx* ctx, int N, int D, int64_t n_segments, const double* coeffs,
+                                        const double* times, const double* windows, int derivative,
+                                        uint32_t dimension_mask, mtg_extremum* minimum, mtg_extremum* maximum,
+                                        double* candidate_times, int32_t* candidate_count, int candidate_capacity,
+                                        int32_t* status, unsigned flags) {
+  return run_segment_extrema(ctx, false, N, D, n_segments, coeffs, times, windows, derivative, dimension_mask, minimum,
+                             maximum, candidate_times, candidate_count, candidate_capacity, status, flags);
+}
+
+int mtg_segment_min_max_axis_batch(mtg_ctx* ctx, int N, int D, int64_t n_segments, const double* coeffs,
+                                   const double* times, const double* windows, int derivative, mtg_extremum* minimum,
+                                   mtg_extremum* maximum, double* candidate_times, int32_t* candidate_count,
+                                   int candidate_capacity, int32_t* status, unsigned flags) {
+  return run_segment_extrema(ctx, true, N, D, n_segments, coeffs, times, windows, derivative, 0, minimum, maximum,
+                             candidate_times, candidate_count, candidate_capacity, status, flags);
+}
+
 int mtg_evaluate_at_path(int N, int D, int K, int64_t M, int n_derivatives) {
   if (int rc = check_order(nullptr, N)) return rc;
   if (int rc = check_dims(nullptr, D, K, M)) return rc;

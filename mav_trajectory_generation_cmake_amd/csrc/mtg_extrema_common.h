@@ -1,6 +1,6 @@
 // mtg_extrema_common.h -- the per-segment extremum search shared by the kernels that need it:
-// mtg_extrema.hip (mtg_min_max_magnitude_batch) and mtg_soft_constraint.hip
-// (mtg_soft_constraint_cost_batch).  One copy of: the staging of q_d = p_d^(k), q1_d = p_d^(k+1) in a
+// mtg_extrema.hip (mtg_min_max_magnitude_batch), mtg_soft_constraint.hip
+// (mtg_soft_constraint_cost_batch) and mtg_segment_extrema.hip (mtg_segment_min_max_*_batch).  One copy of: the staging of q_d = p_d^(k), q1_d = p_d^(k+1) in a
 // group's LDS, the forming of the root polynomial f = sum_d conv(q_d, q1_d), the scan of f on
 // kExtremaSamples + 1 samples, the safeguarded Newton refinement, the magnitude at a candidate and the
 // group's reduction.  The algorithm and its layout are described in mtg_extrema.hip.
@@ -72,6 +72,41 @@ template <int LF>
 __device__ __forceinline__ double refine(const double (&f)[LF], double ta, double tb, double fa, double fb) {
   double a0 = ta, b0 = tb, fa0 = fa, x = ta - fa * ((tb - ta) / (fb - fa));
   if (!(x > ta && x < tb)) x = 0.5 * (ta + tb);
+  for (int it = 0; it < 60; ++it) {
+    double fx = 0.0, dfx = 0.0, ga = 0.0;  // ga: sum |f_j| |x|^j, the scale of f(x)'s rounding error
+    const double ax = fabs(x);
+#pragma unroll
+    for (int j = LF - 1; j >= 0; --j) {
+      dfx = dfx * x + fx;
+      fx = fx * x + f[j];
+      ga = ga * ax + fabs(f[j]);
+    }
+    // f(x) indistinguishable from 0 (below its own evaluation error): converged.  Without this the
+    // Newton steps wander by the rounding noise and only the bisection bound ends them (~45 steps).
+    if (fabs(fx) <= (2.0 * LF * DBL_EPSILON) * ga) break;
+    if ((fx < 0.0) == (fa0 < 0.0)) a0 = x, fa0 = fx;
+    else b0 = x;
+    double xn = x - fx * __builtin_amdgcn_rcp(dfx);  // (a Newton step: an approximate reciprocal will do)
+    if (!(xn > a0 && xn < b0)) xn = 0.5 * (a0 + b0);
+    if (b0 - a0 <= 4.0 * DBL_EPSILON * fmax(fabs(a0), fabs(b0)) || xn == x) {
+      x = xn;
+      break;
+    }
+    x = xn;
+  }
+  return x;
+}
+
+// refine() for the windowed scan, whose sample times are t0 + s h.  In the [0, T] scan ta = (s - 1) h is
+// a product, and the compiler contracts it into tb - ta and ta + tb above (one rounding, not two); the
+// windowed scan hands in the same two FMAs, written out, so that on [0, T] both scans start every
+// refinement from the same point and return the same bits.  (A copy, not a shared body: refine() above
+// must keep compiling to the text the trajectory kernels have always had.)
+template <int LF>
+__device__ __forceinline__ double refine_from(const double (&f)[LF], double ta, double tb, double fa, double fb,
+                                              double width, double sum) {
+  double a0 = ta, b0 = tb, fa0 = fa, x = ta - fa * (width / (fb - fa));
+  if (!(x > ta && x < tb)) x = 0.5 * sum;
   for (int it = 0; it < 60; ++it) {
     double fx = 0.0, dfx = 0.0, ga = 0.0;  // ga: sum |f_j| |x|^j, the scale of f(x)'s rounding error
     const double ax = fabs(x);
@@ -187,29 +222,41 @@ __device__ __forceinline__ double extrema_sumsq_staged(const double* gq, int ndi
   return s;
 }
 
-// This lane's share of the segment's candidates on [0, T]: lane l scans its run of
-// kExtremaSamples / L sample intervals; lane 0 takes t = 0 (order 0) and lane L - 1 takes t = T with
-// order end_ord (end_ord < 0: t = T is not a candidate).  A root found in sample interval s has order
+// The candidates a scan finds go to a sink: begin(pend) once per candidate mask, after the scan has
+// set its bits (bit q: a candidate in sample interval q of the lane's run) and before the first is
+// refined, then put(t, ord) per candidate in ascending order.  The kernels that only need the extremes
+// pass this one, which compiles to nothing.
+struct ExtremaNoSink {
+  __device__ __forceinline__ void begin(uint64_t) const {}
+  __device__ __forceinline__ void put(double, int) const {}
+};
+
+// This lane's share of the segment's candidates on [t0, T] (W: a window with its own start; !W: t0 is
+// not read and the scan runs on [0, T], the text the trajectory kernels have always compiled): lane l
+// scans its run of kExtremaSamples / L sample intervals; lane 0 takes t = t0 (order 0) and lane L - 1
+// takes t = T with order end_ord (end_ord < 0: t = T is not a candidate).  The samples are t0 + s h,
+// h = (T - t0) / kExtremaSamples, the last one T itself.  A root found in sample interval s has order
 // 2 + s.  The scan only sets bits; one loop then takes each lane's candidates lowest bit first (a
 // wave runs the refinement once per candidate a lane holds).  Contract: the caller invokes this only
 // for lanes that own a segment (inside its `if (active)`), and with every such lane of the wave at
 // this call together -- the candidate loop ends on a wave ballot, which counts the executing lanes
 // only, so lanes that skipped the call are not waited for and lanes inside it leave it together.
 // lo / hi: the lane's best candidates so far, updated.
-template <int N, int L, class Mag>
-__device__ __forceinline__ void extrema_scan(const double (&f)[2 * N - 2], double T, int lane, int end_ord, Mag mag,
-                                             Ext& lo, Ext& hi) {
+template <int N, int L, bool W, class Mag, class Sink>
+__device__ __forceinline__ void extrema_scan_on(const double (&f)[2 * N - 2], double t0, double T, int lane,
+                                                int end_ord, Mag mag, Sink& sink, Ext& lo, Ext& hi) {
   constexpr int LF = 2 * N - 2;
   constexpr int SPL = kExtremaSamples / L;  // sample intervals per lane
   constexpr int CH = SPL < 64 ? SPL : 64;   // sample intervals per candidate mask (one bit each)
   constexpr int CS = CH < MTG_EXTREMA_CS ? CH : MTG_EXTREMA_CS;  // sample intervals per unrolled scan step
-  const double h = T / kExtremaSamples;
+  const double h = W ? (T - t0) / kExtremaSamples : T / kExtremaSamples;
+  auto at = [&](int s) { return W ? t0 + s * h : s * h; };  // sample s < kExtremaSamples
   const int s0 = lane * SPL;
-  double fa = horner<LF>(f, s0 * h);
-  // the end points t = 0 (lane 0) and t = T (lane L - 1), in one pass of the wave.
-  // (An exact zero of f at t = 0 or t = T is the same candidate with a later order: never chosen.)
+  double fa = horner<LF>(f, at(s0));
+  // the end points t = t0 (lane 0) and t = T (lane L - 1), in one pass of the wave.
+  // (An exact zero of f at t = t0 or t = T is the same candidate with a later order: never chosen.)
   if (lane == 0 || (lane == L - 1 && end_ord >= 0)) {
-    const double te = lane == 0 ? 0.0 : T;
+    const double te = lane == 0 ? (W ? t0 : 0.0) : T;
     const Ext e{te, mag(te), lane == 0 ? 0 : end_ord};
     lo = hi = e;
   }
@@ -221,29 +268,45 @@ __device__ __forceinline__ void extrema_scan(const double (&f)[2 * N - 2], doubl
 #pragma unroll
       for (int q = 0; q < CS; ++q) {
         const int s = sc + 1 + q0 + q;
-        const double tb = s == kExtremaSamples ? T : s * h;
+        const double tb = s == kExtremaSamples ? T : at(s);
         const double fb = horner<LF>(f, tb);
         const bool hit = fb == 0.0 || (fa < 0.0 && fb > 0.0) || (fa > 0.0 && fb < 0.0);
         pend |= hit ? 1ull << (q0 + q) : 0ull;
         fa = fb;
       }
     }
+    sink.begin(pend);
     // the candidates, lowest bit first, one per lane per round
     while (__builtin_amdgcn_ballot_w64(pend != 0) != 0) {
       if (pend != 0) {
         const int q = __builtin_ctzll(pend);
         pend &= pend - 1;
         const int s = sc + 1 + q;
-        const double tb = s == kExtremaSamples ? T : s * h;
-        const double tl = (s - 1) * h;
+        const double tb = s == kExtremaSamples ? T : at(s);
+        const double tl = at(s - 1);
         const double fl = horner<LF>(f, tl), fb = horner<LF>(f, tb);
-        const double t = fb == 0.0 ? tb : refine<LF>(f, tl, tb, fl, fb);
+        double t;
+        if constexpr (W) {  // tb - tl and tl + tb as the [0, T] scan forms them: (s - 1) h enters unrounded
+          const double sh = (double)(s - 1);
+          t = fb == 0.0 ? tb : refine_from<LF>(f, tl, tb, fl, fb, __builtin_fma(-sh, h, tb - t0), __builtin_fma(sh, h, t0 + tb));
+        } else {
+          t = fb == 0.0 ? tb : refine<LF>(f, tl, tb, fl, fb);
+        }
         const Ext e{t, mag(t), 2 + s};
         if (better_max(e, hi)) hi = e;
         if (better_min(e, lo)) lo = e;
+        sink.put(e.t, e.ord);
       }
     }
   }
+}
+
+// the scan on [0, T] with no sink: the trajectory kernels' call
+template <int N, int L, class Mag>
+__device__ __forceinline__ void extrema_scan(const double (&f)[2 * N - 2], double T, int lane, int end_ord, Mag mag,
+                                             Ext& lo, Ext& hi) {
+  ExtremaNoSink none;
+  extrema_scan_on<N, L, false>(f, 0.0, T, lane, end_ord, mag, none, lo, hi);
 }
 
 // the group's extremes in every lane of the group (lanes of one group are consecutive lanes of one

@@ -1,5 +1,6 @@
 // mtg_host_extrema_common.h -- the host paths' search of one segment for the extremes of a
-// derivative's magnitude, shared by mtg_host_extrema.cpp (Trajectory::computeMinMaxMagnitude) and
+// derivative's magnitude, shared by mtg_host_extrema.cpp (Trajectory::computeMinMaxMagnitude, and the
+// per-segment entries on a window with their candidate lists) and
 // mtg_host_soft_constraint.cpp (PolynomialOptimization::computeMaximumOfMagnitude).  Same algorithm
 // as the HIP kernels (mtg_extrema_common.h): the real roots in [0, T] of
 // sum_d conv(p_d^(k), p_d^(k+1)) (one dimension: of p^(k+1)), isolated by sign changes on 256 uniform
@@ -52,11 +53,23 @@ inline double host_segment_magnitude(int N, int D, const double* cs, int k, unsi
   return std::sqrt(s);
 }
 
-// One segment: cs [D][N], time T, derivative k, dimensions dims.  f, q, q1: work arrays of 2N, N, N
-// doubles.  lo / hi: the segment's minimum and maximum over its candidates.
-inline void host_segment_extrema(int N, int D, const double* cs, double T, int k, unsigned dims,
-                                 SegmentCandidates candidates, double* f, double* q, double* q1, HostExt* lo_out,
-                                 HostExt* hi_out) {
+// signed value of derivative k of dimension d at t (Polynomial::computeMinMax's quantity); cs [D][N]
+inline double host_segment_axis_value(int N, const double* cs, int d, int k, double t) {
+  double acc = 0.0;
+  for (int j = N - k - 1; j >= 0; --j) acc = acc * t + cs[d * N + j + k] * host_falling(j + k, k);
+  return acc;
+}
+
+// One segment on [t0, T] (W: a window with its own start; !W: t0 is not read and the search runs on
+// [0, T], the arithmetic the trajectory entries have always had): cs [D][N], derivative k, dimensions
+// dims.  f, q, q1: work arrays of 2N, N, N doubles; on return f holds the root polynomial and the
+// result is its length.  value(t): the quantity whose extremes are sought; sink(t): called for every
+// root found (an exact zero at t0 included), in ascending order.  lo / hi: the minimum and maximum
+// over the candidates.
+template <bool W, class Value, class Sink>
+inline int host_segment_extrema_on(int N, int D, const double* cs, double t0, double T, int k, unsigned dims,
+                                   SegmentCandidates candidates, double* f, double* q, double* q1, Value value,
+                                   Sink sink, HostExt* lo_out, HostExt* hi_out) {
   const int nd = N - k, ndd = N - k - 1;
   const int ndim = __builtin_popcount(dims);
   for (int j = 0; j < 2 * N; ++j) f[j] = 0.0;
@@ -78,19 +91,24 @@ inline void host_segment_extrema(int N, int D, const double* cs, double T, int k
   }
   HostExt lo{0.0, DBL_MAX}, hi{0.0, -DBL_MAX};
   auto consider = [&](double t) {
-    const double v = host_segment_magnitude(N, D, cs, k, dims, t);
+    const double v = value(t);
     if (v > hi.v) hi = HostExt{t, v};
     if (v < lo.v) lo = HostExt{t, v};
   };
-  consider(0.0);  // the end point(s) first, then the roots in order
+  const double ts = W ? t0 : 0.0;
+  consider(ts);  // the end point(s) first, then the roots in order
   if (candidates == SegmentCandidates::kBothEnds) consider(T);
-  const double h = T / kHostExtremaSamples;
-  double ta = 0.0, fa = host_horner(f, lf, 0.0);
-  if (fa == 0.0) consider(0.0);
+  const double h = W ? (T - t0) / kHostExtremaSamples : T / kHostExtremaSamples;
+  double ta = ts, fa = host_horner(f, lf, ts);
+  if (fa == 0.0) {
+    sink(ts);
+    consider(ts);
+  }
   for (int s = 1; s <= kHostExtremaSamples; ++s) {
-    const double tb = s == kHostExtremaSamples ? T : s * h;
+    const double tb = s == kHostExtremaSamples ? T : (W ? t0 + s * h : s * h);
     const double fb = host_horner(f, lf, tb);
     if (fb == 0.0) {
+      sink(tb);
       consider(tb);
     } else if ((fa < 0.0 && fb > 0.0) || (fa > 0.0 && fb < 0.0)) {
       double a0 = ta, b0 = tb, fa0 = fa, x = ta - fa * ((tb - ta) / (fb - fa));  // from the secant point
@@ -114,6 +132,7 @@ inline void host_segment_extrema(int N, int D, const double* cs, double T, int k
         }
         x = xn;
       }
+      sink(x);
       consider(x);
     }
     ta = tb;
@@ -121,6 +140,16 @@ inline void host_segment_extrema(int N, int D, const double* cs, double T, int k
   }
   *lo_out = lo;
   *hi_out = hi;
+  return lf;
+}
+
+// The trajectory entries' search: [0, T], the magnitude, no candidate list.
+inline void host_segment_extrema(int N, int D, const double* cs, double T, int k, unsigned dims,
+                                 SegmentCandidates candidates, double* f, double* q, double* q1, HostExt* lo_out,
+                                 HostExt* hi_out) {
+  host_segment_extrema_on<false>(
+      N, D, cs, 0.0, T, k, dims, candidates, f, q, q1,
+      [&](double t) { return host_segment_magnitude(N, D, cs, k, dims, t); }, [](double) {}, lo_out, hi_out);
 }
 
 }  // namespace mtg

@@ -245,6 +245,14 @@ hipError_t launch_min_max_magnitude(int N, const double* coeffs, const double* t
                                     int derivative, unsigned dims, mtg_extremum* mn, mtg_extremum* mx,
                                     hipStream_t stream);
 
+// min / max per segment (magnitude) or per (segment, dimension) (axis: signed value) on a window, with
+// the candidate list (mtg_segment_extrema.hip).  coeffs [S][D][N], times [S] (nullable with windows),
+// windows [S][2] (nullable: [0, times[s]]); mn / mx [S] or [S][D], cand [..][cap], count, status [S]:
+// every output nullable
+hipError_t launch_segment_extrema(bool axis, int N, const double* coeffs, const double* times, const double* windows,
+                                  int64_t S, int D, int derivative, unsigned dims, mtg_extremum* mn, mtg_extremum* mx,
+                                  double* cand, int32_t* count, int cap, int32_t* status, hipStream_t stream);
+
 // Trajectory::evaluate at caller-given times (mtg_evaluate_at.hip).  evaluate_at_plan is the one rule
 // that picks the mapping (path: MTG_EVALUATE_AT_LANE or MTG_EVALUATE_AT_STAGED) and the block's
 // threads and LDS bytes from the shape alone; false: a block's rows do not fit in LDS.

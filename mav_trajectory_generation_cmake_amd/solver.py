@@ -760,6 +760,87 @@ class Context:
                                                                _addr(mx), flags), self.handle)
         return mn, mx
 
+    # ------------------------------------------------ per-segment extrema
+    def segment_min_max_magnitude_batch(self, coeffs, times, derivative, dimensions=None, windows=None, **outputs):
+        """Minimum and maximum magnitude of every segment on its window, with the candidate list
+        (include/mtg.h mtg_segment_min_max_magnitude_batch: Segment::computeMinMaxMagnitudeCandidates +
+        selectMinMaxMagnitudeFromCandidates).  coeffs [S][D][N] and times [S] have no trajectory structure: a
+        uniform batch reshaped to [B K] and the CSR arrays of a ragged batch are both valid.  windows [S][2]
+        (t_start, t_end; None: [0, times[s]], and times may be None when windows is given).  numpy arrays or
+        torch CUDA tensors (then every output is a device tensor on torch's current stream; the extrema are
+        uint8 [S][24], see extrema_from_bytes).  outputs: minimum=True, maximum=True, candidate_capacity=0
+        (> 0: candidate_times [S][capacity]), candidate_count=True, status=True, asynchronous=False.  Returns a
+        dict of the requested outputs."""
+        return _segment_extrema(self, False, coeffs, times, derivative, dimensions, windows, **outputs)
+
+    def segment_min_max_axis_batch(self, coeffs, times, derivative, windows=None, **outputs):
+        """Signed minimum and maximum of every (segment, dimension) on its window (mtg_segment_min_max_axis_batch:
+        Polynomial::computeMinMax): arguments and outputs as segment_min_max_magnitude_batch, with minimum /
+        maximum [S][D], candidate_times [S][D][capacity] and candidate_count [S][D]."""
+        return _segment_extrema(self, True, coeffs, times, derivative, None, windows, **outputs)
+
+
+def _segment_extrema(ctx, axis, coeffs, times, derivative, dimensions, windows, minimum=True, maximum=True,
+                     candidate_capacity=0, candidate_count=True, status=True, asynchronous=False, threads=1):
+    """The four per-segment entries; ctx None: the host path."""
+    dev = _is_torch(coeffs) and coeffs.is_cuda
+    S, D, N = (int(x) for x in coeffs.shape)
+    assert times is not None or windows is not None, "times or windows is required"
+    assert times is None or tuple(times.shape) == (S,), "times must be [S]"
+    assert windows is None or tuple(windows.shape) == (S, 2), "windows must be [S][2]"
+    mask = 0 if dimensions is None else int(sum(1 << int(d) for d in dimensions))
+    cap = int(candidate_capacity)
+    item = (S, D) if axis else (S,)
+    if dev:
+        import torch
+        assert ctx is not None, "the host path takes numpy arrays"
+        kw = dict(device=coeffs.device)
+        coeffs = coeffs.contiguous()
+        times = None if times is None else times.contiguous()
+        windows = None if windows is None else windows.contiguous()
+        mn, mx = (torch.zeros(item + (EXTREMUM_DTYPE.itemsize,), dtype=torch.uint8, **kw) if want else None
+                  for want in (minimum, maximum))
+        cand = torch.empty(item + (cap,), dtype=torch.float64, **kw) if cap > 0 else None
+        cnt = torch.empty(item, dtype=torch.int32, **kw) if candidate_count else None
+        stat = torch.empty(S, dtype=torch.int32, **kw) if status else None
+        flags = nat.MTG_FLAG_DEVICE_PTRS | (nat.MTG_FLAG_ASYNC if asynchronous else 0)
+        ctx.set_stream(torch.cuda.current_stream(coeffs.device).cuda_stream)
+    else:
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+        times = None if times is None else np.ascontiguousarray(times, dtype=np.float64)
+        windows = None if windows is None else np.ascontiguousarray(windows, dtype=np.float64)
+        mn, mx = (np.zeros(item, dtype=EXTREMUM_DTYPE) if want else None for want in (minimum, maximum))
+        cand = np.empty(item + (cap,)) if cap > 0 else None
+        cnt = np.empty(item, np.int32) if candidate_count else None
+        stat = np.empty(S, np.int32) if status else None
+        flags = 0
+        if ctx is not None:
+            ctx.reset_stream()
+    head = (N, D, S, _addr(coeffs), _addr(times), _addr(windows), int(derivative))
+    tail = (_addr(mn), _addr(mx), _addr(cand), _addr(cnt), cap, _addr(stat))
+    if ctx is None:
+        lib = nat.load()
+        if axis:
+            nat.check(lib.mtg_host_segment_min_max_axis_batch(*head, *tail, threads))
+        else:
+            nat.check(lib.mtg_host_segment_min_max_magnitude_batch(*head, mask, *tail, threads))
+    elif axis:
+        nat.check(ctx._lib.mtg_segment_min_max_axis_batch(ctx.handle, *head, *tail, flags), ctx.handle)
+    else:
+        nat.check(ctx._lib.mtg_segment_min_max_magnitude_batch(ctx.handle, *head, mask, *tail, flags), ctx.handle)
+    return {"minimum": mn, "maximum": mx, "candidate_times": cand, "candidate_count": cnt, "status": stat}
+
+
+def host_segment_min_max_magnitude_batch(coeffs, times, derivative, dimensions=None, windows=None, **outputs):
+    """Context.segment_min_max_magnitude_batch on the library's host path
+    (mtg_host_segment_min_max_magnitude_batch): no GPU, numpy arrays; outputs also takes threads=1."""
+    return _segment_extrema(None, False, coeffs, times, derivative, dimensions, windows, **outputs)
+
+
+def host_segment_min_max_axis_batch(coeffs, times, derivative, windows=None, **outputs):
+    """Context.segment_min_max_axis_batch on the library's host path (mtg_host_segment_min_max_axis_batch)."""
+    return _segment_extrema(None, True, coeffs, times, derivative, None, windows, **outputs)
+
 
 def extrema_from_bytes(t):
     """The structured array [B] (EXTREMUM_DTYPE) of a device result of min_max_magnitude_ragged_batch (a torch
