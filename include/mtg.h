@@ -397,7 +397,11 @@ int mtg_time_jacobian_batch(mtg_ctx* ctx, int N, int D, int K, int derivative_to
 /* Coefficients from ALL vertex derivatives (fixed and free), nothing solved: per trajectory the
  * reference's setFreeConstraints (polynomial_optimization_linear.h:185-186) followed by
  * updateSegmentsFromCompactConstraints (lin_impl:253-273), c_i = A(T_i)^-1 [x_i; x_{i+1}].
- * vertex_values [B][V][h][D], times [B][K] (> 0) -> coeffs [B][K][D][N]. */
+ * vertex_values [B][V][h][D], times [B][K] (> 0) -> coeffs [B][K][D][N].
+ * Shape limit: a block stages whole trajectories in LDS, 8 * ((K+1)*h*D + K + K*D*N) bytes each, and
+ * needs room for two of them in 48 KiB; otherwise MTG_ERR_TOO_LARGE (nothing is written).  At D = 3 that
+ * is K <= 66 for N = 10 and K <= 55 for N = 12: the long chains (K = 100) are outside this entry
+ * (mtg_host_coefficients_from_vertices_batch has no such limit). */
 int mtg_coefficients_from_vertices_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch,
                                          const double* vertex_values, const double* times, double* coeffs,
                                          unsigned flags);
@@ -406,7 +410,10 @@ int mtg_coefficients_from_vertices_batch(mtg_ctx* ctx, int N, int D, int K, int6
  * (polynomial_optimization_nonlinear_impl.h:162-180, computeInitialSolutionWithoutPositionConstraints;
  * getA / getMpinv, polynomial_optimization_linear.h:209-214): derivative k < h of every segment end,
  * averaged over the two segment ends meeting at an interior vertex.
- * coeffs [B][K][D][N], times [B][K] -> vertex_values [B][V][h][D]. */
+ * coeffs [B][K][D][N], times [B][K] -> vertex_values [B][V][h][D].
+ * Shape limit: that of mtg_coefficients_from_vertices_batch (two trajectories of
+ * 8 * ((K+1)*h*D + K + K*D*N) bytes in 48 KiB of LDS, else MTG_ERR_TOO_LARGE; D = 3: K <= 66 for N = 10,
+ * K <= 55 for N = 12), so the long chains (K = 100) are outside this entry too. */
 int mtg_vertex_derivatives_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* coeffs,
                                  const double* times, double* vertex_values, unsigned flags);
 

@@ -551,8 +551,11 @@ class Context:
         (polynomial_optimization_nonlinear_impl.h:116-187) for a batch: solve, drop every position
         constraint except at the first and last vertex, and start the new free derivatives from the
         solved trajectory (M^+ A p).  Returns dict(mask, values, free [B][D][V*h], n_free, coeffs):
-        the new problem (mask, values) and its free-constraint vector; re-solving it reproduces the
-        same trajectory up to rounding."""
+        the new problem (mask, values) and its free-constraint vector.  Setting that vector back
+        (set_free_constraints_batch) reproduces the solved trajectory up to rounding; re-solving the new
+        problem does not, because the freed interior positions move.  Both vertex maps stage whole
+        trajectories in LDS (include/mtg.h: at D = 3, K <= 66 for N = 10 and K <= 55 for N = 12, else
+        MTG_ERR_TOO_LARGE), so the long chains (K = 100) are outside this function."""
         values = np.ascontiguousarray(values, dtype=np.float64)
         B, V, h, D = values.shape
         sol = self.solve_linear_batch(N, r, values, mask, times)
