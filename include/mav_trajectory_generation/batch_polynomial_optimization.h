@@ -7,8 +7,8 @@
 // derivative k fixed), times [B][K], coeffs [B][K][D][N].  Pass MTG_FLAG_DEVICE_PTRS to hand over
 // device pointers (inputs already in HBM); host pointers are staged by the library.
 // solveRagged takes problems of different segment counts in one call (CSR arrays, include/mtg.h
-// mtg_solve_linear_ragged_batch), and evaluateAtRagged / minMaxMagnitudeRagged consume its coefficients
-// in the same layout: the entries here that are not tied to the object's K.
+// mtg_solve_linear_ragged_batch), and evaluateAtRagged / minMaxMagnitudeRagged / evaluateRangeRagged
+// consume its coefficients in the same layout: the entries here that are not tied to the object's K.
 //
 // Several devices: construct with a device list (e.g. allDevices()).  A host-array solve() is then
 // one mtg_solve_linear_batch_multi call: contiguous shards of the batch, one host thread and one
@@ -340,6 +340,23 @@ class BatchPolynomialOptimization {
     check(mtg_min_max_magnitude_ragged_batch(ctx_, N, D_, batch, seg_count, coeffs, times, derivative, dimension_mask,
                                              minimum, maximum, flags),
           ctx_, "mtg_min_max_magnitude_ragged_batch");
+  }
+  // evaluateRangeCounts and evaluateRange for trajectories of different segment counts
+  // (mtg_evaluate_range_ragged_batch), on the same CSR arrays: counts [batch]; then the samples
+  // [sum counts][D] (+ sampling times) at offsets.  Every trajectory's count, samples and sampling times
+  // are the bytes the uniform members give for it alone.
+  void evaluateRangeRaggedCounts(int64_t batch, const int32_t* seg_count, const double* times, double t_start,
+                                 double t_end, double dt, int64_t* counts, unsigned flags = 0) {
+    check(mtg_evaluate_range_ragged_batch(ctx_, N, D_, batch, seg_count, nullptr, times, t_start, t_end, dt, 0, counts,
+                                          nullptr, nullptr, nullptr, flags),
+          ctx_, "mtg_evaluate_range_ragged_batch(count)");
+  }
+  void evaluateRangeRagged(int64_t batch, const int32_t* seg_count, const double* coeffs, const double* times,
+                           double t_start, double t_end, double dt, int derivative, int64_t* counts,
+                           const int64_t* offsets, double* out, double* sampling_times = nullptr, unsigned flags = 0) {
+    check(mtg_evaluate_range_ragged_batch(ctx_, N, D_, batch, seg_count, coeffs, times, t_start, t_end, dt, derivative,
+                                          counts, offsets, out, sampling_times, flags),
+          ctx_, "mtg_evaluate_range_ragged_batch");
   }
 
  private:

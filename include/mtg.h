@@ -59,7 +59,8 @@ extern "C" {
                                     mtg_host_evaluate_at_ragged_batch, mtg_min_max_magnitude_ragged_batch,
                                     mtg_host_min_max_magnitude_ragged_batch
                                5, additive: + mtg_segment_min_max_magnitude_batch, mtg_segment_min_max_axis_batch,
-                                    mtg_host_segment_min_max_magnitude_batch, mtg_host_segment_min_max_axis_batch */
+                                    mtg_host_segment_min_max_magnitude_batch, mtg_host_segment_min_max_axis_batch
+                               5, additive: + mtg_evaluate_range_ragged_batch, mtg_evaluate_range_ragged_batch_full */
 
 /* Call-level return codes. */
 #define MTG_OK 0
@@ -279,6 +280,46 @@ int mtg_evaluate_range_batch_full(mtg_ctx* ctx, int N, int D, int K, int64_t bat
                                   const double* times, double t_start, double t_end, double dt, int derivative,
                                   int64_t* counts, int64_t* offsets, int64_t* total, double* out,
                                   double* sample_times, int64_t capacity, unsigned flags);
+
+/* mtg_evaluate_range_batch and mtg_evaluate_range_batch_full for a batch whose trajectories have
+ * different segment counts, in the CSR layout of mtg_solve_linear_ragged_batch
+ * (so[b] = sum_{j<b} seg_count[j], 64-bit):
+ *   coeffs [so[b] .. so[b] + K_b][D][N], times [so[b] .. so[b] + K_b]   (as the ragged solve writes them)
+ *   seg_count [B]: a HOST array also with MTG_FLAG_DEVICE_PTRS, read during the call and not kept
+ *   counts, offsets, total, out, sample_times, capacity, the two-call protocol (out == NULL gives
+ *   counts) and the one-call protocol: exactly those of the uniform entries
+ *   t_start, t_end and dt are shared by the batch
+ * Promise: counts[b], every byte of trajectory b's sample rows and every byte of its sample times equal
+ * what mtg_evaluate_range_batch writes for that trajectory alone with K = K_b, whatever the order or
+ * the composition of the batch -- the reference's accumulated clock and unfused Horner, bit for bit.
+ * The CSR indirection is in the kernels: the segment offsets [B + 1] are computed on
+ * the host and uploaded (8 (B + 1) bytes); no coefficient and no time is copied on the device.  A
+ * host-pointer call stages the CSR arrays whole.  Two MTG_FLAG_ASYNC ragged calls of any kind on one
+ * context, with different seg_count, may follow each other without a synchronisation between them.
+ * The clock kernels take 32 trajectories per wave, whose times are one contiguous slice of `times`.
+ * One rule, from seg_count alone, says where they read them: staged in LDS iff
+ *   max over the blocks b0 = 0, 32, 64, ... of sum_{b0 <= b < min(b0 + 32, B)} K_b  <=  32 * 256,
+ * otherwise from global memory.  For a full block of equal K this is the uniform call's rule K <= 256;
+ * a staged trajectory may itself have K_b > 256.  The choice does not change a bit of the result.
+ * The sample kernels (a block per trajectory) are picked, and their LDS sized, by the uniform call's
+ * rule at K_max = max K_b.
+ * Errors, all before any device work: those of the uniform calls on N, D, batch, derivative, dt and
+ * capacity; MTG_ERR_INVALID_ARGUMENT for seg_count == NULL with batch > 0 (and for the required arrays,
+ * as in the uniform calls); MTG_ERR_SIZE_MISMATCH for any seg_count[b] < 1.  When the sample kernels'
+ * LDS at K_max does not fit (N = 10, D = 3: K_max > 250), a call that writes samples returns the
+ * non-zero result of the uniform call at K = K_max (MTG_ERR_HIP, "invalid argument" in
+ * mtg_last_error) and writes nothing; the count call (out == NULL) still succeeds, and the context
+ * serves the next call.  batch == 0: MTG_OK (the one-call form sets *total = 0 when total is given).
+ * A short capacity in the one-call form returns MTG_ERR_TOO_LARGE with counts, offsets and *total
+ * filled and no sample written, as in the uniform call. */
+int mtg_evaluate_range_ragged_batch(mtg_ctx* ctx, int N, int D, int64_t batch, const int32_t* seg_count,
+                                    const double* coeffs, const double* times, double t_start, double t_end,
+                                    double dt, int derivative, int64_t* counts, const int64_t* offsets, double* out,
+                                    double* sample_times, unsigned flags);
+int mtg_evaluate_range_ragged_batch_full(mtg_ctx* ctx, int N, int D, int64_t batch, const int32_t* seg_count,
+                                         const double* coeffs, const double* times, double t_start, double t_end,
+                                         double dt, int derivative, int64_t* counts, int64_t* offsets, int64_t* total,
+                                         double* out, double* sample_times, int64_t capacity, unsigned flags);
 
 /* Batched Trajectory::evaluate (src/trajectory.cpp:41-66) at caller-given query times, several
  * derivative orders from one pass over the coefficients (Polynomial::evaluate(t, VectorXd*),

@@ -157,6 +157,15 @@ _SIGNATURES = {
                                                      ctypes.c_int64, _c_dp, _c_dp, ctypes.c_double, ctypes.c_double,
                                                      ctypes.c_double, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
                                                      ctypes.c_int64, ctypes.c_uint]),
+    "mtg_evaluate_range_ragged_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                       _c_dp, _c_dp, _c_dp, ctypes.c_double, ctypes.c_double,
+                                                       ctypes.c_double, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
+                                                       ctypes.c_uint]),
+    "mtg_evaluate_range_ragged_batch_full": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                            ctypes.c_int64, _c_dp, _c_dp, _c_dp, ctypes.c_double,
+                                                            ctypes.c_double, ctypes.c_double, ctypes.c_int, _c_dp,
+                                                            _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int64,
+                                                            ctypes.c_uint]),
     "mtg_evaluate_at_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                              _c_dp, _c_dp, _c_dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                              ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_uint]),

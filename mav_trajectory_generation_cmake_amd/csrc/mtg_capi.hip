@@ -2206,41 +2206,88 @@ int mtg_evaluate_at_ragged_batch(mtg_ctx* ctx, int N, int D, int64_t batch, cons
   }
 }
 
-int mtg_evaluate_range_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch,
-                             const double* coeffs, const double* times, double t_start,
-                             double t_end, double dt, int derivative, int64_t* counts,
-                             const int64_t* offsets, double* out, double* sample_times,
-                             unsigned flags) {
-  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
-  if (int rc = check_order(ctx, N)) return rc;
-  if (int rc = check_dims(ctx, D, K, batch)) return rc;
-  if (!(dt > 0.0) || derivative < 0)
-    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "dt must be > 0 and derivative >= 0");
-  if (batch == 0) return MTG_OK;
-  if (!times || !counts || (out && (!coeffs || !offsets)))
-    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "times and counts required; out needs coeffs and offsets");
-  std::lock_guard<std::mutex> g(ctx->mu);
+namespace {
+
+// What the uniform and the CSR form of evaluateRange differ in: the shape of coeffs and times, and
+// with it the three launches.  Everything else -- staging, the two-call and the one-call protocol,
+// offsets, capacity -- is one body (run_evaluate_range, run_evaluate_range_full).
+struct EvalShape {
+  int K;        // the segment count; CSR: the largest K_b
+  size_t nseg;  // segments of the whole batch: coeffs [nseg][D][N], times [nseg]
+  const std::vector<int64_t>* so = nullptr;  // CSR: the segment offsets [batch + 1] (host); uniform: null
+  mtg::EvalRagged rag{};                     // CSR: their device copy and the clock's staging rule (eval_shape_begin)
+};
+
+// CSR: the segment offsets to ctx->ragged (mtg_evaluate_at_ragged_batch's mechanism: the only bytes
+// the call makes on the host and uploads besides the caller's arrays), before the first launch.
+int eval_shape_begin(mtg_ctx* ctx, EvalShape* s) {
+  if (!s->so) return MTG_OK;
+  if (int rc = ragged_wait_last(ctx)) return rc;
+  const size_t b_so = sizeof(int64_t) * s->so->size();
+  MTG_HIP_TRY(ctx, ensure(&ctx->ragged, &ctx->ragged_bytes, align_up(b_so)));
+  if (int rc = ragged_upload(ctx, b_so, ctx->ragged, [&](void* p) { std::memcpy(p, s->so->data(), b_so); })) return rc;
+  s->rag.seg_off = static_cast<const int64_t*>(ctx->ragged);
+  s->rag.K_max = s->K;
+  s->rag.clock_slice = mtg::eval_ragged_clock_slice(s->so->data(), (int64_t)s->so->size() - 1);
+  return MTG_OK;
+}
+
+// CSR: after the call's last launch (the next ragged call may run on another stream)
+int eval_shape_end(mtg_ctx* ctx, const EvalShape& s) { return s.so ? ragged_mark_last(ctx) : MTG_OK; }
+
+hipError_t eval_count(const EvalShape& s, int N, int D, int64_t B, const double* times, double t_start, double t_end,
+                      double dt, int64_t* counts, hipStream_t stream) {
+  return s.so ? mtg::launch_eval_count_ragged(s.rag, B, times, t_start, t_end, dt, counts, stream)
+              : mtg::launch_eval_count(N, D, s.K, B, times, t_start, t_end, dt, counts, stream);
+}
+
+hipError_t eval_runs_counts(const EvalShape& s, int64_t B, const double* times, double t_start, double t_end, double dt,
+                            int64_t* counts, int64_t* offsets, void* ws, int cap, int64_t* total, hipStream_t stream) {
+  return s.so ? mtg::launch_eval_runs_counts_ragged(s.rag, B, times, t_start, t_end, dt, counts, offsets, ws, cap, total,
+                                                    stream)
+              : mtg::launch_eval_runs_counts(s.K, B, times, t_start, t_end, dt, counts, offsets, ws, cap, total, stream);
+}
+
+hipError_t eval_range(const EvalShape& s, int N, int D, int64_t B, const double* coeffs, const double* times,
+                      double t_start, double t_end, double dt, int derivative, const int64_t* counts,
+                      const int64_t* offsets, double* out, double* sample_times, void* ws, int cap, hipStream_t stream,
+                      bool runs_ready = false, int64_t* offsets_out = nullptr, int64_t capacity = INT64_MAX,
+                      const int64_t* total = nullptr) {
+  return s.so ? mtg::launch_eval_range_ragged(N, D, s.rag, B, coeffs, times, t_start, t_end, dt, derivative, counts,
+                                              offsets, out, sample_times, ws, cap, stream, runs_ready, offsets_out,
+                                              capacity, total)
+              : mtg::launch_eval_range(N, D, s.K, B, coeffs, times, t_start, t_end, dt, derivative, counts, offsets, out,
+                                       sample_times, ws, cap, stream, runs_ready, offsets_out, capacity, total);
+}
+
+// Body of mtg_evaluate_range_batch and mtg_evaluate_range_ragged_batch, after their argument checks
+// (batch > 0), under ctx->mu.
+int run_evaluate_range(mtg_ctx* ctx, int N, int D, EvalShape& sh, int64_t batch, const double* coeffs,
+                       const double* times, double t_start, double t_end, double dt, int derivative, int64_t* counts,
+                       const int64_t* offsets, double* out, double* sample_times, unsigned flags) {
+  const int K = sh.K;
   MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = eval_shape_begin(ctx, &sh)) return rc;
   const bool dev = flags & MTG_FLAG_DEVICE_PTRS;
   if (dev) {
     if (!out) {
-      MTG_HIP_TRY(ctx, mtg::launch_eval_count(N, D, K, batch, times, t_start, t_end, dt, counts, ctx->stream));
+      MTG_HIP_TRY(ctx, eval_count(sh, N, D, batch, times, t_start, t_end, dt, counts, ctx->stream));
     } else {
       int cap = 0;
       const size_t wsb = mtg::eval_workspace_bytes(K, batch, &cap);
       MTG_HIP_TRY(ctx, ensure(&ctx->workspace, &ctx->workspace_bytes, std::max<size_t>(wsb, 256)));
       MTG_HIP_TRY(ctx, time_begin(ctx, false));  // two kernels: the run table, then the samples
-      MTG_HIP_TRY(ctx, mtg::launch_eval_range(N, D, K, batch, coeffs, times, t_start, t_end, dt, derivative,
-                                              counts, offsets, out, sample_times, ctx->workspace, cap,
-                                              ctx->stream));
+      MTG_HIP_TRY(ctx, eval_range(sh, N, D, batch, coeffs, times, t_start, t_end, dt, derivative, counts, offsets, out,
+                                  sample_times, ctx->workspace, cap, ctx->stream));
       MTG_HIP_TRY(ctx, time_end(ctx));
     }
+    if (int rc = eval_shape_end(ctx, sh)) return rc;
     if (!(flags & MTG_FLAG_ASYNC)) MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return MTG_OK;
   }
   // Host pointers: stage everything.
-  const size_t b_times = sizeof(double) * (size_t)batch * K;
-  const size_t b_coeffs = coeffs ? sizeof(double) * (size_t)batch * K * D * N : 0;
+  const size_t b_times = sizeof(double) * sh.nseg;
+  const size_t b_coeffs = coeffs ? sizeof(double) * sh.nseg * D * N : 0;
   const size_t b_counts = sizeof(int64_t) * (size_t)batch;
   int64_t total = 0;
   if (out) {
@@ -2259,8 +2306,8 @@ int mtg_evaluate_range_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch,
   char* base = static_cast<char*>(ctx->staging);
   MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_times, times, b_times, hipMemcpyHostToDevice, ctx->stream));
   if (!out) {
-    MTG_HIP_TRY(ctx, mtg::launch_eval_count(N, D, K, batch, reinterpret_cast<double*>(base + o_times), t_start,
-                                            t_end, dt, reinterpret_cast<int64_t*>(base + o_counts), ctx->stream));
+    MTG_HIP_TRY(ctx, eval_count(sh, N, D, batch, reinterpret_cast<double*>(base + o_times), t_start, t_end, dt,
+                                reinterpret_cast<int64_t*>(base + o_counts), ctx->stream));
     MTG_HIP_TRY(ctx, hipMemcpyAsync(counts, base + o_counts, b_counts, hipMemcpyDeviceToHost, ctx->stream));
   } else {
     MTG_HIP_TRY(ctx, hipMemcpyAsync(base + o_coeffs, coeffs, b_coeffs, hipMemcpyHostToDevice, ctx->stream));
@@ -2270,34 +2317,28 @@ int mtg_evaluate_range_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch,
     const size_t wsb = mtg::eval_workspace_bytes(K, batch, &cap);
     MTG_HIP_TRY(ctx, ensure(&ctx->workspace, &ctx->workspace_bytes, std::max<size_t>(wsb, 256)));
     MTG_HIP_TRY(ctx, time_begin(ctx, false));
-    MTG_HIP_TRY(ctx, mtg::launch_eval_range(N, D, K, batch, reinterpret_cast<double*>(base + o_coeffs),
-                                            reinterpret_cast<double*>(base + o_times), t_start, t_end, dt,
-                                            derivative, reinterpret_cast<int64_t*>(base + o_counts),
-                                            reinterpret_cast<int64_t*>(base + o_offsets),
-                                            reinterpret_cast<double*>(base + o_out),
-                                            sample_times ? reinterpret_cast<double*>(base + o_st) : nullptr,
-                                            ctx->workspace, cap, ctx->stream));
+    MTG_HIP_TRY(ctx, eval_range(sh, N, D, batch, reinterpret_cast<double*>(base + o_coeffs),
+                                reinterpret_cast<double*>(base + o_times), t_start, t_end, dt, derivative,
+                                reinterpret_cast<int64_t*>(base + o_counts),
+                                reinterpret_cast<int64_t*>(base + o_offsets), reinterpret_cast<double*>(base + o_out),
+                                sample_times ? reinterpret_cast<double*>(base + o_st) : nullptr, ctx->workspace, cap,
+                                ctx->stream));
     MTG_HIP_TRY(ctx, time_end(ctx));
     MTG_HIP_TRY(ctx, hipMemcpyAsync(out, base + o_out, b_out, hipMemcpyDeviceToHost, ctx->stream));
     if (sample_times) MTG_HIP_TRY(ctx, hipMemcpyAsync(sample_times, base + o_st, b_st, hipMemcpyDeviceToHost, ctx->stream));
   }
+  if (int rc = eval_shape_end(ctx, sh)) return rc;
   MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return MTG_OK;
 }
 
-int mtg_evaluate_range_batch_full(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* coeffs,
-                                  const double* times, double t_start, double t_end, double dt, int derivative,
-                                  int64_t* counts, int64_t* offsets, int64_t* total, double* out,
-                                  double* sample_times, int64_t capacity, unsigned flags) {
-  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
-  if (int rc = check_order(ctx, N)) return rc;
-  if (K < 1 || D < 1 || batch < 0 || capacity < 0)
-    return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need K >= 1, D >= 1, batch >= 0, capacity >= 0");
-  if (!(dt > 0.0) || derivative < 0)
-    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "dt must be > 0 and derivative >= 0");
-  if (!coeffs || !times || !counts || !offsets || !total || (capacity > 0 && !out))
-    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "coeffs, times, counts, offsets, total and out are required");
-  std::lock_guard<std::mutex> g(ctx->mu);
+// Body of mtg_evaluate_range_batch_full and mtg_evaluate_range_ragged_batch_full, after their argument
+// checks, under ctx->mu.
+int run_evaluate_range_full(mtg_ctx* ctx, int N, int D, EvalShape& sh, int64_t batch, const double* coeffs,
+                            const double* times, double t_start, double t_end, double dt, int derivative,
+                            int64_t* counts, int64_t* offsets, int64_t* total, double* out, double* sample_times,
+                            int64_t capacity, unsigned flags) {
+  const int K = sh.K;
   MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const bool dev = flags & MTG_FLAG_DEVICE_PTRS;
   if (batch == 0) {
@@ -2305,6 +2346,7 @@ int mtg_evaluate_range_batch_full(mtg_ctx* ctx, int N, int D, int K, int64_t bat
     else *total = 0;
     return MTG_OK;
   }
+  if (int rc = eval_shape_begin(ctx, &sh)) return rc;
   int cap = 0;
   const size_t wsb = mtg::eval_full_workspace_bytes(K, batch, &cap);
   MTG_HIP_TRY(ctx, ensure(&ctx->workspace, &ctx->workspace_bytes, std::max<size_t>(wsb, 256)));
@@ -2313,12 +2355,12 @@ int mtg_evaluate_range_batch_full(mtg_ctx* ctx, int N, int D, int K, int64_t bat
     // counts, offsets (in-block prefix, then final) and the total, then the samples: four kernels on
     // the stream, no host round trip in between
     MTG_HIP_TRY(ctx, time_begin(ctx, false));
-    MTG_HIP_TRY(ctx, mtg::launch_eval_runs_counts(K, batch, times, t_start, t_end, dt, counts, offsets,
-                                                  ctx->workspace, cap, total, ctx->stream));
-    MTG_HIP_TRY(ctx, mtg::launch_eval_range(N, D, K, batch, coeffs, times, t_start, t_end, dt, derivative, counts,
-                                            offsets, out, sample_times, ctx->workspace, cap, ctx->stream, true,
-                                            offsets, capacity, total));
+    MTG_HIP_TRY(ctx, eval_runs_counts(sh, batch, times, t_start, t_end, dt, counts, offsets, ctx->workspace, cap, total,
+                                      ctx->stream));
+    MTG_HIP_TRY(ctx, eval_range(sh, N, D, batch, coeffs, times, t_start, t_end, dt, derivative, counts, offsets, out,
+                                sample_times, ctx->workspace, cap, ctx->stream, true, offsets, capacity, total));
     MTG_HIP_TRY(ctx, time_end(ctx));
+    if (int rc = eval_shape_end(ctx, sh)) return rc;
     if (flags & MTG_FLAG_ASYNC) return MTG_OK;
     int64_t tot = 0;
     MTG_HIP_TRY(ctx, hipMemcpyAsync(&tot, total, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -2348,9 +2390,8 @@ int mtg_evaluate_range_batch_full(mtg_ctx* ctx, int N, int D, int K, int64_t bat
   int64_t* d_cnt = reinterpret_cast<int64_t*>(base + o_cnt);
   int64_t* d_offs = reinterpret_cast<int64_t*>(base + o_offs);
   MTG_HIP_TRY(ctx, time_begin(ctx, false));
-  MTG_HIP_TRY(ctx, mtg::launch_eval_runs_counts(K, batch, reinterpret_cast<const double*>(base + o_times), t_start,
-                                                t_end, dt, d_cnt, d_offs, ctx->workspace, cap, d_total_ws,
-                                                ctx->stream));
+  MTG_HIP_TRY(ctx, eval_runs_counts(sh, batch, reinterpret_cast<const double*>(base + o_times), t_start, t_end, dt,
+                                    d_cnt, d_offs, ctx->workspace, cap, d_total_ws, ctx->stream));
   int64_t tot = 0;
   MTG_HIP_TRY(ctx, hipMemcpyAsync(&tot, d_total_ws, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
   MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -2371,11 +2412,11 @@ int mtg_evaluate_range_batch_full(mtg_ctx* ctx, int N, int D, int K, int64_t bat
     d_offs = reinterpret_cast<int64_t*>(base + o_offs);
   }
   if (tot > capacity) {  // counts, final offsets and the total for the caller's retry; no samples
-    MTG_HIP_TRY(ctx, mtg::launch_eval_range(N, D, K, batch, reinterpret_cast<const double*>(base + o_coef),
-                                            reinterpret_cast<const double*>(base + o_times), t_start, t_end, dt,
-                                            derivative, d_cnt, d_offs, nullptr, nullptr, ctx->workspace, cap,
-                                            ctx->stream, true, d_offs, 0));
+    MTG_HIP_TRY(ctx, eval_range(sh, N, D, batch, reinterpret_cast<const double*>(base + o_coef),
+                                reinterpret_cast<const double*>(base + o_times), t_start, t_end, dt, derivative, d_cnt,
+                                d_offs, nullptr, nullptr, ctx->workspace, cap, ctx->stream, true, d_offs, 0));
     MTG_HIP_TRY(ctx, time_end(ctx));
+    if (int rc = eval_shape_end(ctx, sh)) return rc;
     MTG_HIP_TRY(ctx, hipMemcpyAsync(counts, d_cnt, b_cnt, hipMemcpyDeviceToHost, ctx->stream));
     MTG_HIP_TRY(ctx, hipMemcpyAsync(offsets, d_offs, b_cnt, hipMemcpyDeviceToHost, ctx->stream));
     MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -2384,18 +2425,118 @@ int mtg_evaluate_range_batch_full(mtg_ctx* ctx, int N, int D, int K, int64_t bat
              (long long)capacity);
     return set_error(ctx, MTG_ERR_TOO_LARGE, buf);
   }
-  MTG_HIP_TRY(ctx, mtg::launch_eval_range(N, D, K, batch, reinterpret_cast<const double*>(base + o_coef),
-                                          reinterpret_cast<const double*>(base + o_times), t_start, t_end, dt,
-                                          derivative, d_cnt, d_offs, reinterpret_cast<double*>(base + o_out),
-                                          sample_times ? reinterpret_cast<double*>(base + o_st) : nullptr,
-                                          ctx->workspace, cap, ctx->stream, true, d_offs, capacity));
+  MTG_HIP_TRY(ctx, eval_range(sh, N, D, batch, reinterpret_cast<const double*>(base + o_coef),
+                              reinterpret_cast<const double*>(base + o_times), t_start, t_end, dt, derivative, d_cnt,
+                              d_offs, reinterpret_cast<double*>(base + o_out),
+                              sample_times ? reinterpret_cast<double*>(base + o_st) : nullptr, ctx->workspace, cap,
+                              ctx->stream, true, d_offs, capacity));
   MTG_HIP_TRY(ctx, time_end(ctx));
+  if (int rc = eval_shape_end(ctx, sh)) return rc;
   MTG_HIP_TRY(ctx, hipMemcpyAsync(counts, d_cnt, b_cnt, hipMemcpyDeviceToHost, ctx->stream));
   MTG_HIP_TRY(ctx, hipMemcpyAsync(offsets, d_offs, b_cnt, hipMemcpyDeviceToHost, ctx->stream));
   if (b_out) MTG_HIP_TRY(ctx, hipMemcpyAsync(out, base + o_out, b_out, hipMemcpyDeviceToHost, ctx->stream));
   if (b_st) MTG_HIP_TRY(ctx, hipMemcpyAsync(sample_times, base + o_st, b_st, hipMemcpyDeviceToHost, ctx->stream));
   MTG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return MTG_OK;
+}
+
+// The checks the two CSR evaluateRange entries share after their own on N, D, batch and capacity: dt
+// and derivative, then seg_count (ragged_check_counts), then -- for a call that writes samples -- the
+// sample kernels' LDS at the largest K_b, with the result of the uniform call at that K and its HIP
+// error text in the message.  All before any device work.
+int eval_ragged_check(mtg_ctx* ctx, int N, int D, int64_t batch, const int32_t* seg_count, double dt, int derivative,
+                      bool samples, int* k_max, std::vector<int64_t>* so) {
+  if (!(dt > 0.0) || derivative < 0)
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "dt must be > 0 and derivative >= 0");
+  if (int rc = ragged_check_counts(ctx, batch, seg_count, k_max, so)) return rc;
+  if (batch > 0 && samples) MTG_HIP_TRY(ctx, mtg::eval_range_lds_check(N, D, *k_max));
+  return MTG_OK;
+}
+
+}  // namespace
+
+int mtg_evaluate_range_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch,
+                             const double* coeffs, const double* times, double t_start,
+                             double t_end, double dt, int derivative, int64_t* counts,
+                             const int64_t* offsets, double* out, double* sample_times,
+                             unsigned flags) {
+  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
+  if (int rc = check_order(ctx, N)) return rc;
+  if (int rc = check_dims(ctx, D, K, batch)) return rc;
+  if (!(dt > 0.0) || derivative < 0)
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "dt must be > 0 and derivative >= 0");
+  if (batch == 0) return MTG_OK;
+  if (!times || !counts || (out && (!coeffs || !offsets)))
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "times and counts required; out needs coeffs and offsets");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  EvalShape sh{K, (size_t)batch * K};
+  return run_evaluate_range(ctx, N, D, sh, batch, coeffs, times, t_start, t_end, dt, derivative, counts, offsets, out,
+                            sample_times, flags);
+}
+
+int mtg_evaluate_range_batch_full(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* coeffs,
+                                  const double* times, double t_start, double t_end, double dt, int derivative,
+                                  int64_t* counts, int64_t* offsets, int64_t* total, double* out,
+                                  double* sample_times, int64_t capacity, unsigned flags) {
+  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
+  if (int rc = check_order(ctx, N)) return rc;
+  if (K < 1 || D < 1 || batch < 0 || capacity < 0)
+    return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need K >= 1, D >= 1, batch >= 0, capacity >= 0");
+  if (!(dt > 0.0) || derivative < 0)
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "dt must be > 0 and derivative >= 0");
+  if (!coeffs || !times || !counts || !offsets || !total || (capacity > 0 && !out))
+    return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "coeffs, times, counts, offsets, total and out are required");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  EvalShape sh{K, (size_t)batch * K};
+  return run_evaluate_range_full(ctx, N, D, sh, batch, coeffs, times, t_start, t_end, dt, derivative, counts, offsets,
+                                 total, out, sample_times, capacity, flags);
+}
+
+int mtg_evaluate_range_ragged_batch(mtg_ctx* ctx, int N, int D, int64_t batch, const int32_t* seg_count,
+                                    const double* coeffs, const double* times, double t_start, double t_end,
+                                    double dt, int derivative, int64_t* counts, const int64_t* offsets, double* out,
+                                    double* sample_times, unsigned flags) {
+  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
+  if (int rc = check_order(ctx, N)) return rc;
+  if (D < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need D >= 1, batch >= 0");
+  try {
+    int k_max = 0;
+    std::vector<int64_t> so;
+    if (int rc = eval_ragged_check(ctx, N, D, batch, seg_count, dt, derivative, out != nullptr, &k_max, &so)) return rc;
+    if (batch == 0) return MTG_OK;
+    if (!times || !counts || (out && (!coeffs || !offsets)))
+      return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "times and counts required; out needs coeffs and offsets");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    EvalShape sh{k_max, (size_t)so.back(), &so};
+    return run_evaluate_range(ctx, N, D, sh, batch, coeffs, times, t_start, t_end, dt, derivative, counts, offsets, out,
+                              sample_times, flags);
+  } catch (const std::bad_alloc&) {
+    return set_error(ctx, MTG_ERR_OUT_OF_MEMORY, "ragged evaluateRange: out of host memory");
+  }
+}
+
+int mtg_evaluate_range_ragged_batch_full(mtg_ctx* ctx, int N, int D, int64_t batch, const int32_t* seg_count,
+                                         const double* coeffs, const double* times, double t_start, double t_end,
+                                         double dt, int derivative, int64_t* counts, int64_t* offsets, int64_t* total,
+                                         double* out, double* sample_times, int64_t capacity, unsigned flags) {
+  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
+  if (int rc = check_order(ctx, N)) return rc;
+  if (D < 1 || batch < 0 || capacity < 0)
+    return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need D >= 1, batch >= 0, capacity >= 0");
+  try {
+    int k_max = 0;
+    std::vector<int64_t> so;
+    if (int rc = eval_ragged_check(ctx, N, D, batch, seg_count, dt, derivative, true, &k_max, &so)) return rc;
+    if (batch == 0 && !total) return MTG_OK;
+    if (batch > 0 && (!coeffs || !times || !counts || !offsets || !total || (capacity > 0 && !out)))
+      return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "coeffs, times, counts, offsets, total and out are required");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    EvalShape sh{std::max(k_max, 1), batch ? (size_t)so.back() : 0, &so};
+    return run_evaluate_range_full(ctx, N, D, sh, batch, coeffs, times, t_start, t_end, dt, derivative, counts, offsets,
+                                   total, out, sample_times, capacity, flags);
+  } catch (const std::bad_alloc&) {
+    return set_error(ctx, MTG_ERR_OUT_OF_MEMORY, "ragged evaluateRange: out of host memory");
+  }
 }
 
 int mtg_last_kernel_ms(mtg_ctx* ctx, float* ms) {

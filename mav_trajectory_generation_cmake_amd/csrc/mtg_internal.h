@@ -296,5 +296,34 @@ size_t eval_full_workspace_bytes(int K, int64_t B, int* cap);
 hipError_t launch_eval_runs_counts(int K, int64_t B, const double* times, double t_start, double t_end, double dt,
                                    int64_t* counts, int64_t* offsets, void* ws, int cap, int64_t* total,
                                    hipStream_t stream);
+// eval_scan_kernel alone (mtg_eval.hip): nb block totals in bsum, scanned in place, and the grand total
+void launch_eval_scan(int64_t nb, int64_t* bsum, int64_t* total, hipStream_t stream);
+
+// evaluateRange on a CSR batch (mtg_eval_ragged.hip): the same three launches, with trajectory b's
+// segments at seg_off[b] .. seg_off[b + 1] of coeffs [sum K][D][N] and times [sum K].  The workspace
+// is that of the uniform launches (it does not depend on K).
+struct EvalRagged {
+  const int64_t* seg_off;  // [B + 1], a device array
+  int K_max;               // the largest K_b: it sizes the sample kernels' LDS and picks among them
+  int64_t clock_slice;     // eval_ragged_clock_slice of the (host) offsets
+};
+// The clock kernels' staging rule: the most segments of any 32-trajectory block, from the host copy of
+// seg_off; the times are staged in LDS when that is at most 32 * 256, else read from global memory.
+int64_t eval_ragged_clock_slice(const int64_t* seg_off, int64_t B);
+bool eval_ragged_clock_staged(int64_t clock_slice);
+// hipErrorInvalidValue when the sample kernels' LDS at K segments does not fit (launch_eval_range's
+// error at that K), without launching anything
+hipError_t eval_range_lds_check(int N, int D, int K);
+hipError_t launch_eval_count_ragged(const EvalRagged& r, int64_t B, const double* times, double t_start, double t_end,
+                                    double dt, int64_t* counts, hipStream_t stream);
+hipError_t launch_eval_runs_counts_ragged(const EvalRagged& r, int64_t B, const double* times, double t_start,
+                                          double t_end, double dt, int64_t* counts, int64_t* offsets, void* ws, int cap,
+                                          int64_t* total, hipStream_t stream);
+hipError_t launch_eval_range_ragged(int N, int D, const EvalRagged& r, int64_t B, const double* coeffs,
+                                    const double* times, double t_start, double t_end, double dt, int derivative,
+                                    const int64_t* counts, const int64_t* offsets, double* out, double* sample_times,
+                                    void* ws, int cap, hipStream_t stream, bool runs_ready = false,
+                                    int64_t* offsets_out = nullptr, int64_t capacity = INT64_MAX,
+                                    const int64_t* total = nullptr);
 
 }  // namespace mtg

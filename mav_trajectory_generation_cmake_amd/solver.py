@@ -733,6 +733,81 @@ class Context:
                                                          _addr(in_range), _addr(status), flags), self.handle)
         return out, in_range, status
 
+    def evaluate_range_ragged_batch(self, coeffs, times, seg_count, t_start, t_end, dt, derivative=0, want_times=True):
+        """evaluate_range_batch for a batch of different segment counts (mtg_evaluate_range_ragged_batch, the
+        two-call form on host arrays): coeffs [sum K][D][N], times [sum K], seg_count [B].  Returns (samples
+        [S][D], sample_times [S] or None, counts [B], offsets [B]); every trajectory's samples are the bytes
+        evaluate_range_batch gives for it alone.  coeffs and times may also be lists of per-trajectory blocks
+        (split_ragged)."""
+        coeffs = np.ascontiguousarray(_csr(coeffs), dtype=np.float64)
+        times = np.ascontiguousarray(_csr(times), dtype=np.float64)
+        seg_count, B, D, N = _ragged_coeff_shape(coeffs, times, seg_count)
+        counts = np.zeros(B, dtype=np.int64)
+        self.reset_stream()
+        nat.check(self._lib.mtg_evaluate_range_ragged_batch(self.handle, N, D, B, _addr(seg_count), None, _addr(times),
+                                                            float(t_start), float(t_end), float(dt), int(derivative),
+                                                            _addr(counts), None, None, None, 0), self.handle)
+        offsets = np.zeros(B, dtype=np.int64)
+        if B > 1:
+            offsets[1:] = np.cumsum(counts)[:-1]
+        total = int(counts.sum())
+        out = np.zeros((max(total, 1), D))
+        st = np.zeros(max(total, 1)) if want_times else None
+        nat.check(self._lib.mtg_evaluate_range_ragged_batch(self.handle, N, D, B, _addr(seg_count), _addr(coeffs),
+                                                            _addr(times), float(t_start), float(t_end), float(dt),
+                                                            int(derivative), _addr(counts), _addr(offsets), _addr(out),
+                                                            _addr(st), 0), self.handle)
+        return out[:total], (st[:total] if want_times else None), counts, offsets
+
+    def evaluate_range_ragged_batch_full(self, coeffs, times, seg_count, t_start, t_end, dt, derivative=0,
+                                         want_times=True, capacity=None, asynchronous=False):
+        """evaluate_range_batch_full for a batch of different segment counts
+        (mtg_evaluate_range_ragged_batch_full): the CSR arrays coeffs [sum K][D][N] and times [sum K] as
+        Context.solve_linear_ragged_batch returns them (numpy or torch-device), seg_count [B] a host array
+        either way.  capacity, the retry, asynchronous and the result are those of evaluate_range_batch_full."""
+        coeffs, times = _csr(coeffs), _csr(times)
+        dev = _is_torch(coeffs) and coeffs.is_cuda
+        seg_count, B, D, N = _ragged_coeff_shape(coeffs, times, seg_count)
+        if capacity is None:
+            capacity = evaluate_range_capacity(times, t_start, t_end, dt, seg_count=seg_count)
+        for attempt in range(2):
+            if dev:
+                import torch
+                kw = dict(device=coeffs.device)
+                coeffs, times = coeffs.contiguous(), times.contiguous()
+                counts = torch.empty(B, dtype=torch.int64, **kw)
+                offsets = torch.empty(B, dtype=torch.int64, **kw)
+                total = torch.zeros(1, dtype=torch.int64, **kw)
+                out = torch.empty((max(capacity, 1), D), dtype=torch.float64, **kw)
+                st = torch.empty(max(capacity, 1), dtype=torch.float64, **kw) if want_times else None
+                flags = nat.MTG_FLAG_DEVICE_PTRS | (nat.MTG_FLAG_ASYNC if asynchronous else 0)
+                self.set_stream(torch.cuda.current_stream(coeffs.device).cuda_stream)
+            else:
+                coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+                times = np.ascontiguousarray(times, dtype=np.float64)
+                counts = np.empty(B, dtype=np.int64)
+                offsets = np.empty(B, dtype=np.int64)
+                total = np.zeros(1, dtype=np.int64)
+                out = np.empty((max(capacity, 1), D))
+                st = np.empty(max(capacity, 1)) if want_times else None
+                flags = 0
+                self.reset_stream()
+            rc = self._lib.mtg_evaluate_range_ragged_batch_full(self.handle, N, D, B, _addr(seg_count), _addr(coeffs),
+                                                                _addr(times), float(t_start), float(t_end), float(dt),
+                                                                int(derivative), _addr(counts), _addr(offsets),
+                                                                _addr(total), _addr(out), _addr(st), int(capacity),
+                                                                flags)
+            if dev and asynchronous:
+                nat.check(rc, self.handle)
+                return out, st, counts, offsets, total
+            if rc == nat.MTG_ERR_TOO_LARGE and attempt == 0:
+                capacity = int(total[0])
+                continue
+            nat.check(rc, self.handle)
+            break
+        n = int(total[0])
+        return out[:n], (st[:n] if want_times else None), counts, offsets
+
     def min_max_magnitude_ragged_batch(self, coeffs, times, seg_count, derivative, dimensions=None, minimum=True,
                                        maximum=True, asynchronous=False):
         """min_max_magnitude_batch for a batch of different segment counts
@@ -911,14 +986,22 @@ def host_evaluate_at_batch(coeffs, times, t_query, derivative_begin=0, n_derivat
     return out, in_range, status
 
 
-def evaluate_range_capacity(times, t_start, t_end, dt):
+def evaluate_range_capacity(times, t_start, t_end, dt, seg_count=None):
     """A safe sample capacity for evaluateRange over a batch (mtg_evaluate_range_batch_full): per
     trajectory the clock samples while the accumulated time (>= 0) is below t_end and the sample is
     inside the trajectory, so at most min(t_end, sum T) / dt + 2 samples; 1e-9 relative slack for the
-    rounding of the accumulated clock."""
+    rounding of the accumulated clock.  times [B][K], or with seg_count [B] the CSR array [sum K]
+    (mtg_evaluate_range_ragged_batch_full): the same bound per trajectory, summed."""
     if _is_torch(times):
         times = times.detach().cpu().numpy()
-    span = np.minimum(np.asarray(times, dtype=np.float64).sum(axis=1), float(t_end))
+    times = np.asarray(times, dtype=np.float64)
+    if seg_count is None:
+        duration = times.sum(axis=1)
+    else:
+        seg_count = np.asarray(seg_count, dtype=np.int64).reshape(-1)
+        assert (seg_count >= 1).all() and times.shape == (int(seg_count.sum()),), "times must be [sum K], K_b >= 1"
+        duration = np.add.reduceat(times, np.cumsum(seg_count) - seg_count) if len(seg_count) else np.zeros(0)
+    span = np.minimum(duration, float(t_end))
     n = np.floor(np.maximum(span, 0.0) / float(dt) * (1.0 + 1e-9)) + 3
     return int(n.sum())
 
