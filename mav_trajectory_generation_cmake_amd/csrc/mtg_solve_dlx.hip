@@ -16,8 +16,8 @@ MTG_DLX_DECL(12, 1) MTG_DLX_DECL(12, 2) MTG_DLX_DECL(12, 3) MTG_DLX_DECL(12, 4)
 
 // Shapes the kernel serves: N = 6 .. 12, D <= 4, r >= 1 (translation-relative positions), K >= 2, where
 // neither the fixed-length DL kernel (N = 10 / 12: K = 10 / 20) nor the register column kernel (N = 6 /
-// 8: K <= 12; N = 10: K <= 10; N = 12: K <= 20) applies, and only where the general kernel's geometry
-// exists (it solves the complement).
+// 8: K <= 12; N = 10: K <= 10; N = 12: K <= 8 and 13 <= K <= 20) applies, and only where the general
+// kernel's geometry exists (it solves the complement).  
 bool dlx_geometry(int N, int D, int K, int r) {
   if (N < 6 || N > 12 || (N % 2) || D < 1 || D > 4 || r < 1 || r > N / 2 - 1 || K < 2) return false;
   int lg, tpb;

@@ -105,16 +105,24 @@ def truth_solve(N, r, vals, mask, times):
     return coeffs, float(cost / 2), free_out, fixed_out
 
 
-def truth_solve_banded(N, r, vals, mask, times):
+def truth_solve_banded(N, r, vals, mask, times, full=False, system=None):
     """truth_solve's coefficients for long chains: the same 60-digit system (_system), R_pp solved by a
     banded LDL^T elimination (R_pp is block tridiagonal in the reference's (vertex, derivative) order,
     SPD, so no pivoting) instead of a dense LU -- O(n bw^2) instead of O(n^3) multiprecision operations
     (N = 10, K = 64: ~1 s instead of ~80 s).  Same digits: the tests use it where truth_solve is too
-    slow (tests/test_oracle.py checks the two agree)."""
+    slow (tests/test_oracle.py checks the two agree).
+
+    full=True returns (coeffs, free [D][n_free], cost, cost_per_dimension [D]) instead of the
+    coefficients alone: the free derivatives in the reference's (vertex, derivative) order (truth_solve's
+    third output), the cost 0.5 sum c^T Q c (its second) and that sum's part of every dimension (the
+    dimensions are independent problems: a D-dimensional problem's truth holds the truth of every
+    problem made of some of its dimensions).  system: a _system(N, r, vals, mask, times) result computed
+    before (it does not depend on the values), to share it with fp64_best_solve."""
+    mp.mp.dps = DPS
     h = N // 2
     V, nd, D = vals.shape
     K = V - 1
-    R, fixed, free, col, Ainvs, Qs = _system(N, r, vals, mask, times)
+    R, fixed, free, col, Ainvs, Qs = system if system is not None else _system(N, r, vals, mask, times)
     nf, npf = len(fixed), len(free)
     A = [[R[nf + a][nf + b] for b in range(npf)] for a in range(npf)]
     bw = 0
@@ -132,6 +140,8 @@ def truth_solve_banded(N, r, vals, mask, times):
                 A[j][k] -= f * A[i][k]
             A[j][i] = f
     coeffs = np.zeros((K, D, N))
+    free_out = np.zeros((D, npf))
+    cost_d = [mp.mpf(0)] * D
     for d in range(D):
         df = [mp.mpf(float(vals[v, k, d])) for (v, k) in fixed]
         x = [-mp.fsum(R[nf + a][b] * df[b] for b in range(nf)) for a in range(npf)]
@@ -144,24 +154,29 @@ def truth_solve_banded(N, r, vals, mask, times):
                 t -= A[j][i] * x[j]
             x[i] = t
         dall = df + x
+        free_out[d] = [float(v) for v in x]
         for i in range(K):
             cols = [col[(i + (s >= h), s % h)] for s in range(N)]
             c = Ainvs[i] * mp.matrix([dall[c] for c in cols])
             coeffs[i, d] = [float(c[j]) for j in range(N)]
+            if full:
+                cost_d[d] += (c.T * Qs[i] * c)[0, 0]
+    if full:
+        return coeffs, free_out, float(mp.fsum(cost_d) / 2), np.array([float(v / 2) for v in cost_d])
     return coeffs
 
 
-def fp64_best_solve(N, r, vals, mask, times):
+def fp64_best_solve(N, r, vals, mask, times, system=None):
     """What a backward-stable FP64 solve reaches on this problem: R_pp and the right-hand side formed
     exactly (60 digits) and rounded once to FP64, equilibrated (symmetric diagonal scaling), solved
     by LU with partial pivoting (LAPACK via numpy), and mapped to coefficients with the correctly
     rounded A(T)^-1 in FP64, positions taken relative to each segment's start (else the mapping alone
     loses every digit of a millimetre segment far from the origin).  The arbiter for ill-conditioned problems (cond(R_pp) ~ 1e10 after
-    equilibration): no FP64 solver can be expected to beat it by much."""
+    equilibration): no FP64 solver can be expected to beat it by much.  (system: as truth_solve_banded's.)"""
     h = N // 2
     V, nd, D = vals.shape
     K = V - 1
-    R, fixed, free, col, Ainvs, Qs = _system(N, r, vals, mask, times)
+    R, fixed, free, col, Ainvs, Qs = system if system is not None else _system(N, r, vals, mask, times)
     nf, npf = len(fixed), len(free)
     coeffs = np.zeros((K, D, N))
     Rf = np.array([[float(R[nf + a][nf + b]) for b in range(npf)] for a in range(npf)])

@@ -19,10 +19,11 @@ pytestmark = pytest.mark.gpu
 TRUTH_TOL = 1e-9
 ORACLE_TOL_N10 = 1e-6
 
-# the solve paths behind mtg_solve_linear_batch: the default (mtg_solve_kernel: the register column
-# kernel for K <= 12 and for N = 12 up to K = 20, else the general one; the dimension-lane kernel for
-# the shapes it serves), the general LDS-resident fused kernel, the two-kernel split path, the
-# dimension-lane kernel asked for (MTG_FLAG_DL_KERNEL, where it applies) and the column kernel asked for
+# the solve paths behind mtg_solve_linear_batch: the default (mtg_solve_kernel, DESIGN.md 3.0: the
+# dimension-lane kernel at the shapes it serves; the register column kernel for K <= 12 at N <= 8, K <= 10
+# at N = 10 and K <= 8 or 13..20 at N = 12; beyond those the long-chain kernel where it applies, else the
+# general one), the general LDS-resident fused kernel, the two-kernel split path, the dimension-lane
+# kernels asked for (MTG_FLAG_DL_KERNEL, where they apply) and the column kernel asked for
 PATHS = {"default": {}, "general": {"general": True}, "split": {"split": True}, "dl": {"dl": True},
          "column": {"column": True}}
 

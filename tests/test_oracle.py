@@ -125,6 +125,34 @@ def test_truth_banded_matches_dense_truth():
             assert err <= 1e-15, (case, b, err)
 
 
+def test_truth_banded_full_matches_dense_truth():
+    """truth_solve_banded(full=True) -- the coefficients, the free derivatives in the reference's (vertex,
+    derivative) order and the cost, which tests/_solve_truth_cases.py holds every solve kernel to -- equals
+    the dense-LU truth_solve on small shapes of that grid (every mask kind, n_free = 0 among them),
+    exactly after rounding; the cost's parts per dimension sum to it; and a system passed in (shared with
+    fp64_best_solve) changes nothing."""
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    from make_golden import _system, fp64_best_solve, truth_solve, truth_solve_banded
+    import _solve_truth_cases as C
+    for N, r, K, kind in [(2, 0, 3, "mixed"), (4, 1, 4, "ends"), (6, 0, 3, "mixed"), (8, 2, 5, "mixed"),
+                          (10, 4, 1, "pattern"), (10, 3, 4, "ends"), (12, 5, 3, "mixed"), (12, 0, 4, "pattern")]:
+        vals, mask, times = C.problems(N, r, K, kind)
+        for p in range(C.PROBLEMS):
+            c, cost, free, _ = truth_solve(N, r, vals[p], mask[p], times[p])
+            bc, bfree, bcost, bcost_d = truth_solve_banded(N, r, vals[p], mask[p], times[p], full=True)
+            assert scale_normalised_error(bc[None], c[None], times[p][None]) <= 1e-15
+            assert bfree.shape == free.shape == (vals.shape[-1], C.n_free_of(N, mask[p]))
+            np.testing.assert_allclose(bfree, free, rtol=1e-15, atol=0)
+            assert abs(bcost - cost) <= 1e-15 * cost and abs(bcost_d.sum() - cost) <= 1e-14 * cost
+            np.testing.assert_array_equal(truth_solve_banded(N, r, vals[p], mask[p], times[p]), bc)
+            system = _system(N, r, vals[p], mask[p], times[p])
+            sc = truth_solve_banded(N, r, vals[p], mask[p], times[p], full=True, system=system)
+            np.testing.assert_array_equal(sc[0], bc)
+            np.testing.assert_array_equal(sc[1], bfree)
+            np.testing.assert_array_equal(fp64_best_solve(N, r, vals[p], mask[p], times[p], system=system),
+                                          fp64_best_solve(N, r, vals[p], mask[p], times[p]))
+
+
 def _setup(N, r, vals, mask, times):
     res = O.solve_linear(N, r, vals, mask, times, want_matrices=True)
     K = len(times)
