@@ -7,7 +7,8 @@
 // derivative k fixed), times [B][K], coeffs [B][K][D][N].  Pass MTG_FLAG_DEVICE_PTRS to hand over
 // device pointers (inputs already in HBM); host pointers are staged by the library.
 // solveRagged takes problems of different segment counts in one call (CSR arrays, include/mtg.h
-// mtg_solve_linear_ragged_batch), and evaluateAtRagged / minMaxMagnitudeRagged / evaluateRangeRagged
+// mtg_solve_linear_ragged_batch), and evaluateAtRagged / minMaxMagnitudeRagged / evaluateRangeRagged /
+// vertexDerivativesRagged / coefficientsFromVerticesRagged / collisionCostRagged
 // consume its coefficients in the same layout: the entries here that are not tied to the object's K.
 //
 // Several devices: construct with a device list (e.g. allDevices()).  A host-array solve() is then
@@ -359,6 +360,33 @@ class BatchPolynomialOptimization {
           ctx_, "mtg_evaluate_range_ragged_batch");
   }
 
+  // The two vertex <-> coefficient maps and the collision cost for trajectories of different segment
+  // counts (mtg_vertex_derivatives_ragged_batch, mtg_coefficients_from_vertices_ragged_batch,
+  // mtg_collision_cost_ragged_batch) on the same CSR arrays: vertex_values [sum K + batch][h][D] and mask
+  // [sum K + batch] hold trajectory b's V_b rows at so[b] + b, grad is its block [3][V_b h] at double
+  // offset 3 h (so[b] + b) (solveRagged's free layout), cost / is_collision / n_evaluated / status are
+  // [batch].  Every trajectory's outputs are the bytes the uniform member gives for it alone; the maps
+  // have no limit on K.  The object's `segments` is not used.
+  void vertexDerivativesRagged(int64_t batch, const int32_t* seg_count, const double* coeffs, const double* times,
+                               double* vertex_values, unsigned flags = 0) {
+    check(mtg_vertex_derivatives_ragged_batch(ctx_, N, D_, batch, seg_count, coeffs, times, vertex_values, flags), ctx_,
+          "mtg_vertex_derivatives_ragged_batch");
+  }
+  void coefficientsFromVerticesRagged(int64_t batch, const int32_t* seg_count, const double* vertex_values,
+                                      const double* times, double* coeffs, unsigned flags = 0) {
+    check(mtg_coefficients_from_vertices_ragged_batch(ctx_, N, D_, batch, seg_count, vertex_values, times, coeffs,
+                                                      flags),
+          ctx_, "mtg_coefficients_from_vertices_ragged_batch");
+  }
+  void collisionCostRagged(int64_t batch, const int32_t* seg_count, const double* vertex_values, const uint8_t* mask,
+                           const double* times, const mtg_sdf_grid& grid, const mtg_collision_params& params,
+                           double* cost, double* grad = nullptr, uint8_t* is_collision = nullptr,
+                           int32_t* n_evaluated = nullptr, int32_t* status = nullptr, unsigned flags = 0) {
+    check(mtg_collision_cost_ragged_batch(ctx_, N, D_, batch, seg_count, vertex_values, mask, times, &grid, &params,
+                                          cost, grad, is_collision, n_evaluated, status, flags),
+          ctx_, "mtg_collision_cost_ragged_batch");
+  }
+
  private:
   int D_, K_, r_;
   std::vector<mtg_ctx*> ctxs_;
@@ -572,6 +600,55 @@ inline void minMaxMagnitudeRagged(int D, int64_t batch, const int32_t* seg_count
     check(mtg_host_min_max_magnitude_ragged_batch(N, D, batch, seg_count, coeffs, times, derivative, dimension_mask,
                                                   minimum, maximum, 1),
           nullptr, "mtg_host_min_max_magnitude_ragged_batch");
+  }
+}
+
+// vertexDerivatives, coefficientsFromVertices and collisionCost<N> for trajectories of different segment
+// counts in the CSR layout (vertex_values [sum K + batch][h][D], mask [sum K + batch], coeffs
+// [sum K][D][N], times [sum K], seg_count [batch]; grad: trajectory b's block [3][V_b h] at double offset
+// 3 h (so[b] + b)), without a BatchPolynomialOptimization object: on the library's host paths unless the
+// execution policy is kDevice, as collisionCost.  Host pointers.
+template <int N>
+inline void vertexDerivativesRagged(int D, int64_t batch, const int32_t* seg_count, const double* coeffs,
+                                    const double* times, double* vertex_values) {
+  if (singleOnDevice()) {
+    mtg_ctx* ctx = defaultContext();
+    check(mtg_vertex_derivatives_ragged_batch(ctx, N, D, batch, seg_count, coeffs, times, vertex_values, 0), ctx,
+          "mtg_vertex_derivatives_ragged_batch");
+  } else {
+    check(mtg_host_vertex_derivatives_ragged_batch(N, D, batch, seg_count, coeffs, times, vertex_values, 1), nullptr,
+          "mtg_host_vertex_derivatives_ragged_batch");
+  }
+}
+
+template <int N>
+inline void coefficientsFromVerticesRagged(int D, int64_t batch, const int32_t* seg_count, const double* vertex_values,
+                                           const double* times, double* coeffs) {
+  if (singleOnDevice()) {
+    mtg_ctx* ctx = defaultContext();
+    check(mtg_coefficients_from_vertices_ragged_batch(ctx, N, D, batch, seg_count, vertex_values, times, coeffs, 0), ctx,
+          "mtg_coefficients_from_vertices_ragged_batch");
+  } else {
+    check(mtg_host_coefficients_from_vertices_ragged_batch(N, D, batch, seg_count, vertex_values, times, coeffs, 1),
+          nullptr, "mtg_host_coefficients_from_vertices_ragged_batch");
+  }
+}
+
+template <int N>
+inline void collisionCostRagged(int64_t batch, const int32_t* seg_count, const double* vertex_values,
+                                const uint8_t* mask, const double* times, const mtg_sdf_grid& grid,
+                                const mtg_collision_params& params, double* cost, double* grad = nullptr,
+                                uint8_t* is_collision = nullptr, int32_t* n_evaluated = nullptr,
+                                int32_t* status = nullptr) {
+  if (singleOnDevice()) {
+    mtg_ctx* ctx = defaultContext();
+    check(mtg_collision_cost_ragged_batch(ctx, N, 3, batch, seg_count, vertex_values, mask, times, &grid, &params, cost,
+                                          grad, is_collision, n_evaluated, status, 0),
+          ctx, "mtg_collision_cost_ragged_batch");
+  } else {
+    check(mtg_host_collision_cost_ragged_batch(N, 3, batch, seg_count, vertex_values, mask, times, &grid, &params, cost,
+                                               grad, is_collision, n_evaluated, status, 1),
+          nullptr, "mtg_host_collision_cost_ragged_batch");
   }
 }
 

@@ -60,7 +60,13 @@ extern "C" {
                                     mtg_host_min_max_magnitude_ragged_batch
                                5, additive: + mtg_segment_min_max_magnitude_batch, mtg_segment_min_max_axis_batch,
                                     mtg_host_segment_min_max_magnitude_batch, mtg_host_segment_min_max_axis_batch
-                               5, additive: + mtg_evaluate_range_ragged_batch, mtg_evaluate_range_ragged_batch_full */
+                               5, additive: + mtg_evaluate_range_ragged_batch, mtg_evaluate_range_ragged_batch_full
+                               5, additive: + mtg_coefficients_from_vertices_ragged_batch,
+                                    mtg_vertex_derivatives_ragged_batch, mtg_vertex_ragged_tile,
+                                    mtg_collision_cost_ragged_batch, mtg_host_vertex_derivatives_batch,
+                                    mtg_host_vertex_derivatives_ragged_batch,
+                                    mtg_host_coefficients_from_vertices_ragged_batch,
+                                    mtg_host_collision_cost_ragged_batch */
 
 /* Call-level return codes. */
 #define MTG_OK 0
@@ -458,6 +464,34 @@ int mtg_coefficients_from_vertices_batch(mtg_ctx* ctx, int N, int D, int K, int6
 int mtg_vertex_derivatives_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* coeffs,
                                  const double* times, double* vertex_values, unsigned flags);
 
+/* The two maps for a batch whose trajectories have different segment counts, on the CSR layout of
+ * mtg_solve_linear_ragged_batch: K_b = seg_count[b] >= 1, V_b = K_b + 1, so[b] = sum_{j<b} K_j,
+ * vo[b] = so[b] + b (both 64-bit).  seg_count [B] is a host array, also with MTG_FLAG_DEVICE_PTRS.
+ *   mtg_coefficients_from_vertices_ragged_batch  (setFreeConstraints,
+ *       polynomial_optimization_linear.h:185-186, + updateSegmentsFromCompactConstraints, lin_impl:253-273)
+ *       vertex_values [vo[b] .. vo[b]+V_b][h][D], times [so[b] .. so[b]+K_b] -> coeffs [so[b] .. so[b]+K_b][D][N]
+ *   mtg_vertex_derivatives_ragged_batch  (M^+ A p, nl_impl:162-180)
+ *       coeffs, times as above -> vertex_values: the mean of the two segment ends at an interior vertex,
+ *       the single end at the first or last vertex of its trajectory.
+ * Every output byte of trajectory b equals what the uniform entry writes for that trajectory alone,
+ * where the uniform entry accepts that K.  There is no limit on K: a block owns a fixed tile of
+ * mtg_vertex_ragged_tile(N, D) consecutive packed segments, whatever trajectory borders fall inside
+ * it, so its LDS use depends on N and D only and a K = 100 chain goes through.  MTG_ERR_TOO_LARGE only
+ * where not even one segment's arrays fit the staging (a D in the hundreds).
+ * Errors, all raised before any device work: those of the uniform calls on N, D and batch;
+ * MTG_ERR_INVALID_ARGUMENT for seg_count == NULL with batch > 0; MTG_ERR_SIZE_MISMATCH for a
+ * seg_count[b] < 1.  batch == 0 returns MTG_OK.  Flags: MTG_FLAG_DEVICE_PTRS, MTG_FLAG_ASYNC; two
+ * MTG_FLAG_ASYNC ragged calls of any kind may follow each other on one context. */
+int mtg_coefficients_from_vertices_ragged_batch(mtg_ctx* ctx, int N, int D, int64_t batch, const int32_t* seg_count,
+                                                const double* vertex_values, const double* times, double* coeffs,
+                                                unsigned flags);
+int mtg_vertex_derivatives_ragged_batch(mtg_ctx* ctx, int N, int D, int64_t batch, const int32_t* seg_count,
+                                        const double* coeffs, const double* times, double* vertex_values,
+                                        unsigned flags);
+/* Packed segments per block of the two entries above (> 0), or MTG_ERR_UNSUPPORTED_N,
+ * MTG_ERR_SIZE_MISMATCH (D < 1), MTG_ERR_TOO_LARGE.  For tests and tools. */
+int mtg_vertex_ragged_tile(int N, int D);
+
 /* Extremum of a trajectory (the reference's Extremum, extremum.h): segment-local time, value and
  * segment index. */
 typedef struct mtg_extremum {
@@ -633,6 +667,37 @@ int mtg_host_collision_cost_batch(int N, int D, int K, int64_t batch, const doub
                                   const uint8_t* fixed_mask, const double* times, const mtg_sdf_grid* grid,
                                   const mtg_collision_params* params, double* cost_out, double* grad_out,
                                   uint8_t* collision_out, int32_t* n_evaluated_out, int32_t* status, int threads);
+
+/* getCostAndGradientCollision (nl_impl:1523-1709) for a batch whose trajectories have different
+ * segment counts: J_c, its gradient and the is_collision flag of every candidate in one call, on the
+ * CSR layout of mtg_solve_linear_ragged_batch (K_b = seg_count[b] >= 1, V_b = K_b + 1,
+ * so[b] = sum_{j<b} K_j, vo[b] = so[b] + b; seg_count [B] is a host array, also with
+ * MTG_FLAG_DEVICE_PTRS).  vertex_values [vo[b] .. vo[b]+V_b][h][3] and fixed_mask [vo[b] ..] are
+ * indexed at vo[b], times at so[b]; cost_out, collision_out, n_evaluated_out and status are [B];
+ * grad_out is the block [3][V_b h] at double offset 3 h vo[b] -- the layout of the ragged solve's
+ * free_out, so the two add -- and is zeroed by the call.  Semantics, nullable outputs, per-trajectory
+ * status, flags and grid staging are those of mtg_collision_cost_batch, and every output byte of
+ * trajectory b equals what that entry writes for the trajectory alone.
+ * One launch of B one-wave blocks whose LDS is sized for the largest K_b: MTG_ERR_TOO_LARGE, before
+ * any device work, when that exceeds 64 KiB (N = 10: K_max > 172).  A batch holding one long chain
+ * therefore runs its short trajectories at the long chain's occupancy.
+ * Errors: those of mtg_collision_cost_batch (D != 3, dt <= 0, ...); MTG_ERR_INVALID_ARGUMENT for
+ * seg_count == NULL with batch > 0; MTG_ERR_SIZE_MISMATCH for a seg_count[b] < 1.  batch == 0 returns
+ * MTG_OK.  Two MTG_FLAG_ASYNC ragged calls of any kind may follow each other on one context. */
+int mtg_collision_cost_ragged_batch(mtg_ctx* ctx, int N, int D, int64_t batch, const int32_t* seg_count,
+                                    const double* vertex_values, const uint8_t* fixed_mask, const double* times,
+                                    const mtg_sdf_grid* grid, const mtg_collision_params* params, double* cost_out,
+                                    double* grad_out, uint8_t* collision_out, int32_t* n_evaluated_out, int32_t* status,
+                                    unsigned flags);
+
+/* Host (CPU) path of mtg_collision_cost_ragged_batch: the per-trajectory code of
+ * mtg_host_collision_cost_batch on each trajectory's blocks of the CSR arrays, threaded over
+ * trajectories; a trajectory's bytes are those of that entry with batch 1. */
+int mtg_host_collision_cost_ragged_batch(int N, int D, int64_t batch, const int32_t* seg_count,
+                                         const double* vertex_values, const uint8_t* fixed_mask, const double* times,
+                                         const mtg_sdf_grid* grid, const mtg_collision_params* params, double* cost_out,
+                                         double* grad_out, uint8_t* collision_out, int32_t* n_evaluated_out,
+                                         int32_t* status, int threads);
 
 /* Segment-time gradient of the collision cost: the dJc_dt part of getCostAndGradientTime
  * (nl_impl:2155-2243), the central difference of J_c in each segment time, restated as the reference
@@ -1162,6 +1227,24 @@ int mtg_host_segment_matrices(int N, int derivative_to_optimize, double T, doubl
  * vertex_values [B][V][h][D] (all derivatives), times [B][K] -> coeffs [B][K][D][N]. */
 int mtg_host_coefficients_from_vertices_batch(int N, int D, int K, int64_t batch, const double* vertex_values,
                                               const double* times, double* coeffs, int threads);
+
+/* Host form of mtg_vertex_derivatives_batch (M^+ A p, nl_impl:162-180) in scalar C++: the end
+ * derivatives of every segment by Horner with the base coefficients j!/(j-k)! (polynomial.h:120-151),
+ * the mean of the two ends that meet at an interior vertex.  coeffs [B][K][D][N], times [B][K] ->
+ * vertex_values [B][V][h][D]; any K.  threads <= 0: mtg_host_default_threads(). */
+int mtg_host_vertex_derivatives_batch(int N, int D, int K, int64_t batch, const double* coeffs, const double* times,
+                                      double* vertex_values, int threads);
+
+/* Host forms of the two CSR maps (mtg_vertex_derivatives_ragged_batch,
+ * mtg_coefficients_from_vertices_ragged_batch): the uniform host code on each trajectory's blocks,
+ * threaded over trajectories; a trajectory's bytes are those of the uniform host entry with batch 1.
+ * The errors on N, D, batch and seg_count are the device entries'. */
+int mtg_host_vertex_derivatives_ragged_batch(int N, int D, int64_t batch, const int32_t* seg_count,
+                                             const double* coeffs, const double* times, double* vertex_values,
+                                             int threads);
+int mtg_host_coefficients_from_vertices_ragged_batch(int N, int D, int64_t batch, const int32_t* seg_count,
+                                                     const double* vertex_values, const double* times, double* coeffs,
+                                                     int threads);
 
 #ifdef __cplusplus
 }

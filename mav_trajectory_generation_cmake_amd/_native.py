@@ -143,6 +143,26 @@ _SIGNATURES = {
     "mtg_host_min_max_magnitude_ragged_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, _c_dp, _c_dp,
                                                                _c_dp, ctypes.c_int, ctypes.c_uint32, _c_dp, _c_dp,
                                                                ctypes.c_int]),
+    "mtg_coefficients_from_vertices_ragged_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                                   ctypes.c_int64, _c_dp, _c_dp, _c_dp, _c_dp,
+                                                                   ctypes.c_uint]),
+    "mtg_vertex_derivatives_ragged_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                           _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_uint]),
+    "mtg_vertex_ragged_tile": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "mtg_collision_cost_ragged_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                       _c_dp, _c_dp, _c_dp, _c_dp, ctypes.POINTER(SdfGrid),
+                                                       ctypes.POINTER(CollisionParams), _c_dp, _c_dp, _c_dp, _c_dp,
+                                                       _c_dp, ctypes.c_uint]),
+    "mtg_host_collision_cost_ragged_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, _c_dp, _c_dp,
+                                                            _c_dp, _c_dp, ctypes.POINTER(SdfGrid),
+                                                            ctypes.POINTER(CollisionParams), _c_dp, _c_dp, _c_dp,
+                                                            _c_dp, _c_dp, ctypes.c_int]),
+    "mtg_host_vertex_derivatives_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                         _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mtg_host_vertex_derivatives_ragged_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, _c_dp,
+                                                                _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mtg_host_coefficients_from_vertices_ragged_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                                        _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mtg_shard_range": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
                                        ctypes.POINTER(ctypes.c_int64)]),
     "mtg_solve_linear_batch_multi": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,

@@ -1461,6 +1461,63 @@ int mtg_collision_cost_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, c
   return st.finish();
 }
 
+int mtg_collision_cost_ragged_batch(mtg_ctx* ctx, int N, int D, int64_t batch, const int32_t* seg_count,
+                                    const double* vertex_values, const uint8_t* fixed_mask, const double* times,
+                                    const mtg_sdf_grid* grid, const mtg_collision_params* params, double* cost_out,
+                                    double* grad_out, uint8_t* collision_out, int32_t* n_evaluated_out, int32_t* status,
+                                    unsigned flags) {
+  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
+  if (int rc = check_collision(ctx, N, D, 1, batch, grid, params)) return rc;
+  if (batch == 0) return MTG_OK;
+  try {
+    int k_max = 0;
+    std::vector<int64_t> so;
+    if (int rc = ragged_check_counts(ctx, batch, seg_count, &k_max, &so)) return rc;
+    if (!vertex_values || !times || !cost_out || !grid->distance || (grad_out && !fixed_mask))
+      return set_error(ctx, MTG_ERR_INVALID_ARGUMENT,
+                       "vertex_values, times, cost_out and grid->distance are required; grad_out needs fixed_mask");
+    if (mtg::collision_lds_bytes(N, k_max) > 64 * 1024)
+      return set_error(ctx, MTG_ERR_TOO_LARGE, "the longest trajectory's coefficients exceed LDS (reduce its K)");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // one launch on the caller's CSR arrays: nothing is copied on the device
+    const int h = N / 2;
+    const size_t nB = (size_t)batch, totS = (size_t)so.back(), totV = totS + nB;
+    const size_t b_grad = sizeof(double) * totV * D * h;
+    const double *d_vals, *d_times;
+    const uint8_t* d_mask;
+    const float* d_grid;
+    double *d_cost, *d_grad;
+    uint8_t* d_coll;
+    int32_t *d_nev, *d_stat;
+    Staged st(ctx, flags);
+    st.in(&d_vals, vertex_values, sizeof(double) * totV * h * D);
+    st.in(&d_mask, fixed_mask, grad_out ? totV : 0);
+    st.in(&d_times, times, sizeof(double) * totS);
+    st.in(&d_grid, grid->distance, grid_bytes(*grid));
+    st.out(&d_cost, cost_out, sizeof(double) * nB);
+    st.out(&d_grad, grad_out, b_grad);
+    st.out(&d_coll, collision_out, nB);
+    st.out(&d_nev, n_evaluated_out, sizeof(int32_t) * nB);
+    st.out(&d_stat, status, sizeof(int32_t) * nB);
+    if (int rc = ragged_wait_last(ctx)) return rc;
+    if (int rc = st.upload()) return rc;
+    const size_t b_so = sizeof(int64_t) * so.size();
+    MTG_HIP_TRY(ctx, ensure(&ctx->ragged, &ctx->ragged_bytes, align_up(b_so)));
+    if (int rc = ragged_upload(ctx, b_so, ctx->ragged, [&](void* p) { std::memcpy(p, so.data(), b_so); })) return rc;
+    if (d_grad) MTG_HIP_TRY(ctx, hipMemsetAsync(d_grad, 0, b_grad, ctx->stream));
+    MTG_HIP_TRY(ctx, time_begin(ctx));
+    MTG_HIP_TRY(ctx, mtg::launch_collision_cost_ragged(N, k_max, batch, static_cast<const int64_t*>(ctx->ragged), d_vals,
+                                                       d_mask, d_times, *grid, d_grid, *params, d_cost, d_grad, d_coll,
+                                                       d_nev, d_stat, ctx->stream));
+    MTG_HIP_TRY(ctx, time_end(ctx));
+    if (int rc = ragged_mark_last(ctx)) return rc;
+    return st.finish();
+  } catch (const std::bad_alloc&) {
+    return set_error(ctx, MTG_ERR_OUT_OF_MEMORY, "ragged collision cost: out of host memory");
+  }
+}
+
 int mtg_collision_time_gradient_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* vertex_values,
                                       const double* times, const mtg_sdf_grid* grid, const mtg_collision_params* params,
                                       double increment_time, double* grad_t_out, double* side_cost_out,
@@ -1999,6 +2056,71 @@ int mtg_coefficients_from_vertices_batch(mtg_ctx* ctx, int N, int D, int K, int6
 int mtg_vertex_derivatives_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* coeffs,
                                  const double* times, double* vertex_values, unsigned flags) {
   return run_vertex_map(ctx, false, N, D, K, batch, coeffs, times, vertex_values, flags);
+}
+
+namespace {
+
+// Shared body of the two maps on a CSR batch: [sum K + B][h][D] <-> [sum K][D][N].
+// The segment offsets go to ctx->ragged, then one launch over tiles of packed segments.
+int run_vertex_map_ragged(mtg_ctx* ctx, bool to_coeffs, int N, int D, int64_t batch, const int32_t* seg_count,
+                          const double* in, const double* times, double* out, unsigned flags) {
+  if (!ctx) return MTG_ERR_INVALID_ARGUMENT;
+  if (int rc = check_order(ctx, N)) return rc;
+  if (D < 1 || batch < 0) return set_error(ctx, MTG_ERR_SIZE_MISMATCH, "need D >= 1, batch >= 0");
+  if (mtg::vertex_ragged_tile(N, D) < 1)
+    return set_error(ctx, MTG_ERR_TOO_LARGE, "one segment's arrays exceed the LDS staging (reduce D)");
+  if (batch == 0) return MTG_OK;
+  try {
+    int k_max = 0;
+    std::vector<int64_t> so;
+    if (int rc = ragged_check_counts(ctx, batch, seg_count, &k_max, &so)) return rc;
+    if (!in || !times || !out) return set_error(ctx, MTG_ERR_INVALID_ARGUMENT, "input, times and output are required");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int h = N / 2;
+    const size_t nB = (size_t)batch, totS = (size_t)so.back();
+    const size_t b_vals = sizeof(double) * (totS + nB) * h * D, b_coef = sizeof(double) * totS * D * N;
+    const double *d_in, *d_times;
+    double* d_out;
+    Staged st(ctx, flags);
+    st.in(&d_in, in, to_coeffs ? b_vals : b_coef);
+    st.in(&d_times, times, sizeof(double) * totS);
+    st.out(&d_out, out, to_coeffs ? b_coef : b_vals);
+    if (int rc = ragged_wait_last(ctx)) return rc;
+    if (int rc = st.upload()) return rc;
+    const size_t b_so = sizeof(int64_t) * so.size();
+    MTG_HIP_TRY(ctx, ensure(&ctx->ragged, &ctx->ragged_bytes, align_up(b_so)));
+    if (int rc = ragged_upload(ctx, b_so, ctx->ragged, [&](void* p) { std::memcpy(p, so.data(), b_so); })) return rc;
+    MTG_HIP_TRY(ctx, time_begin(ctx));
+    MTG_HIP_TRY(ctx, mtg::launch_vertex_map_ragged(to_coeffs, N, d_in, d_times, static_cast<const int64_t*>(ctx->ragged),
+                                                   d_out, batch, so.back(), D, ctx->stream));
+    MTG_HIP_TRY(ctx, time_end(ctx));
+    if (int rc = ragged_mark_last(ctx)) return rc;
+    return st.finish();
+  } catch (const std::bad_alloc&) {
+    return set_error(ctx, MTG_ERR_OUT_OF_MEMORY, "ragged vertex map: out of host memory");
+  }
+}
+
+}  // namespace
+
+int mtg_coefficients_from_vertices_ragged_batch(mtg_ctx* ctx, int N, int D, int64_t batch, const int32_t* seg_count,
+                                                const double* vertex_values, const double* times, double* coeffs,
+                                                unsigned flags) {
+  return run_vertex_map_ragged(ctx, true, N, D, batch, seg_count, vertex_values, times, coeffs, flags);
+}
+
+int mtg_vertex_derivatives_ragged_batch(mtg_ctx* ctx, int N, int D, int64_t batch, const int32_t* seg_count,
+                                        const double* coeffs, const double* times, double* vertex_values,
+                                        unsigned flags) {
+  return run_vertex_map_ragged(ctx, false, N, D, batch, seg_count, coeffs, times, vertex_values, flags);
+}
+
+int mtg_vertex_ragged_tile(int N, int D) {
+  if (N < 2 || N > 12 || (N % 2)) return MTG_ERR_UNSUPPORTED_N;
+  if (D < 1) return MTG_ERR_SIZE_MISMATCH;
+  const int ts = mtg::vertex_ragged_tile(N, D);
+  return ts < 1 ? MTG_ERR_TOO_LARGE : ts;
 }
 
 int mtg_min_max_magnitude_batch(mtg_ctx* ctx, int N, int D, int K, int64_t batch, const double* coeffs,

@@ -188,6 +188,50 @@ extern "C" int mtg_host_collision_cost_batch(int N, int D, int K, int64_t batch,
              n_evaluated_out, status, threads);
 }
 
+// Host path of mtg_collision_cost_ragged_batch: the same per-trajectory code on each trajectory's blocks
+// of the CSR arrays (vertices and mask at so[b] + b, times at so[b], the gradient block [3][V_b h] at
+// double offset 3 h (so[b] + b)), threaded over trajectories.
+extern "C" int mtg_host_collision_cost_ragged_batch(int N, int D, int64_t batch, const int32_t* seg_count,
+                                                    const double* vertex_values, const uint8_t* fixed_mask,
+                                                    const double* times, const mtg_sdf_grid* grid,
+                                                    const mtg_collision_params* params, double* cost_out,
+                                                    double* grad_out, uint8_t* collision_out, int32_t* n_evaluated_out,
+                                                    int32_t* status, int threads) {
+  if (N < 6 || N > 12 || (N % 2)) return MTG_ERR_UNSUPPORTED_N;
+  if (D != 3) return MTG_ERR_INVALID_ARGUMENT;
+  if (batch < 0) return MTG_ERR_SIZE_MISMATCH;
+  if (!grid || !params) return MTG_ERR_INVALID_ARGUMENT;
+  if (!(params->coll_check_time_increment > 0.0) || !(params->map_resolution >= 0.0) || !(grid->resolution > 0.0) ||
+      grid->nx < 1 || grid->ny < 1 || grid->nz < 1)
+    return MTG_ERR_INVALID_ARGUMENT;
+  if (batch == 0) return MTG_OK;
+  if (!seg_count) return MTG_ERR_INVALID_ARGUMENT;
+  std::vector<int64_t> so((size_t)batch + 1, 0);
+  for (int64_t b = 0; b < batch; ++b) {
+    if (seg_count[b] < 1) return MTG_ERR_SIZE_MISMATCH;
+    so[(size_t)b + 1] = so[(size_t)b] + seg_count[b];
+  }
+  if (!vertex_values || !times || !cost_out || !grid->distance || (grad_out && !fixed_mask)) return MTG_ERR_INVALID_ARGUMENT;
+  const mtg::CollisionMap map{grid->distance, grid->nx, grid->ny, grid->nz,
+                              {grid->origin[0], grid->origin[1], grid->origin[2]}, grid->resolution, grid->oob_distance};
+  const mtg::CollisionPot pot{params->map_resolution, params->epsilon, params->robot_radius, params->coll_pot_multiplier,
+                              {params->min_bound[0], params->min_bound[1], params->min_bound[2]},
+                              {params->max_bound[0], params->max_bound[1], params->max_bound[2]},
+                              params->use_continuous_distance ? 1 : 0};
+  const double dt = params->coll_check_time_increment;
+  const int h = N / 2;
+  mtg::run_threads(batch, threads, [&](int64_t b0, int64_t b1) {
+    Work w;
+    for (int64_t b = b0; b < b1; ++b) {
+      const int64_t s0 = so[(size_t)b], v0 = s0 + b;
+      one(N, seg_count[b], vertex_values + v0 * h * D, fixed_mask ? fixed_mask + v0 : nullptr, times + s0, nullptr, map,
+          pot, dt, cost_out + b, grad_out ? grad_out + v0 * D * h : nullptr, collision_out ? collision_out + b : nullptr,
+          n_evaluated_out ? n_evaluated_out + b : nullptr, status ? status + b : nullptr, w);
+    }
+  });
+  return MTG_OK;
+}
+
 int mtg::host_collision_cost_coeff_times(int N, int D, int K, int64_t batch, const double* vertex_values,
                                          const double* times, const double* coeff_times, const mtg_sdf_grid* grid,
                                          const mtg_collision_params* params, double* cost_out, uint8_t* collision_out,

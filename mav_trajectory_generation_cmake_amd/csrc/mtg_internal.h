@@ -139,6 +139,16 @@ hipError_t launch_collision_cost(int N, const double* values, const uint8_t* mas
                                  double* cost, double* grad, uint8_t* collision, int32_t* n_evaluated, int32_t* status,
                                  int64_t B, int K, hipStream_t stream, const double* coeff_times = nullptr);
 
+// the same for a CSR batch (mtg_collision_ragged.hip): trajectory b's segments are seg_off[b] ..
+// seg_off[b + 1] of times [sum K], its vertices the rows seg_off[b] + b .. of values [sum K + B][h][3] and
+// mask [sum K + B], its gradient block [3][V_b h] at double offset 3 h (seg_off[b] + b); seg_off [B + 1]
+// is a device array.  One launch whose LDS is collision_lds_bytes(N, K_max), K_max the largest K_b.
+hipError_t launch_collision_cost_ragged(int N, int K_max, int64_t B, const int64_t* seg_off, const double* values,
+                                        const uint8_t* mask, const double* times, const mtg_sdf_grid& grid,
+                                        const float* distance, const mtg_collision_params& p, double* cost,
+                                        double* grad, uint8_t* collision, int32_t* n_evaluated, int32_t* status,
+                                        hipStream_t stream);
+
 // segment-time gradient of the collision cost (mtg_collision_time.hip); `distance` is the device copy
 // of grid.distance
 size_t collision_time_lds_bytes(int N, int K);
@@ -239,6 +249,14 @@ hipError_t launch_objective_time_combine(const ObjectiveTimeCombineArgs& a, hipS
 bool vertex_map_fits(int N, int D, int K);
 hipError_t launch_vertex_map(bool to_coeffs, int N, const double* in, const double* times, double* out, int64_t B,
                              int K, int D, hipStream_t stream);
+
+// the same for a CSR batch (mtg_vertex_ragged.hip): coeffs [S][D][N], times [S], values [S + B][h][D]
+// with S = seg_off[B] segments in all; a block owns vertex_ragged_tile(N, D) consecutive packed
+// segments (0: a single segment's arrays exceed the LDS staging), whatever K the trajectories have
+int vertex_ragged_tile(int N, int D);
+hipError_t launch_vertex_map_ragged(bool to_coeffs, int N, const double* in, const double* times,
+                                    const int64_t* seg_off, double* out, int64_t B, int64_t S, int D,
+                                    hipStream_t stream);
 
 // min / max magnitude of a derivative over trajectories (mtg_extrema.hip)
 hipError_t launch_min_max_magnitude(int N, const double* coeffs, const double* times, int64_t B, int K, int D,

@@ -13,7 +13,8 @@
 //   computeInitialSolutionWithoutPositionConstraints): the end derivatives A_i c_i of every
 //   segment, mapped to the (vertex, derivative) unknowns by the pseudo-inverse of the 0/1
 //   reordering matrix M (lin_impl:172-250), i.e. the mean of the two segment ends that meet at an
-//   interior vertex and the single end at the first / last vertex.
+//   interior vertex and the single end at the first / last vertex.  The per-(vertex, derivative,
+//   dimension) part is mtg_vertex_common.h too, shared with mtg_vertex_ragged.hip.
 //
 // Both are HBM-bound streams.  A block of 256 threads owns TB consecutive trajectories: it
 // stages their input (contiguous in HBM) into LDS with coalesced loads, computes one item per
@@ -22,34 +23,7 @@
 
 namespace mtg {
 
-constexpr int kVtxThreads = 256;
-
 namespace {
-
-// dst[i] = src[i] for i < n by the block, U loads per thread in flight before the stores.
-template <int U>
-__device__ __forceinline__ void stage_copy(const double* __restrict__ src, double* dst, int n, int tid) {
-  for (int base = 0; base < n; base += U * kVtxThreads) {
-    double r[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int i = base + u * kVtxThreads + tid;
-      r[u] = src[i < n ? i : n - 1];
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int i = base + u * kVtxThreads + tid;
-      if (i < n) dst[i] = r[u];
-    }
-  }
-}
-
-// falling factorial k!/(k-n)! (Polynomial::base_coefficients_, src/polynomial.cpp:140-155)
-__device__ __forceinline__ double falling(int k, int n) {
-  double f = 1.0;
-  for (int q = 0; q < n; ++q) f *= (double)(k - q);
-  return f;
-}
 
 // vertex values [TB][V][H][D] -> coefficients [TB][K][D][N]
 template <int N>
@@ -102,21 +76,9 @@ __global__ __launch_bounds__(kVtxThreads) void vertex_derivatives_kernel(const d
   for (int it = tid; it < nb * xsz; it += kVtxThreads) {
     const int bl = it / xsz, rem = it - bl * xsz;
     const int v = rem / (H * D), r2 = rem - v * (H * D), k = r2 / D, d = r2 - k * D;
-    double sum = 0.0;
-    int cnt = 0;
-    if (v < K) {  // start of segment v: p^(k)(0) = k! c_k
-      sum += falling(k, k) * co[((bl * K + v) * D + d) * N + k];
-      ++cnt;
-    }
-    if (v > 0) {  // end of segment v-1: p^(k)(T) = sum_j j!/(j-k)! c_j T^(j-k)  (Horner)
-      const double T = tl[bl * K + v - 1];
-      const double* c = co + ((bl * K + v - 1) * D + d) * N;
-      double acc = 0.0;
-      for (int j = N - 1; j >= k; --j) acc = acc * T + falling(j, k) * c[j];
-      sum += acc;
-      ++cnt;
-    }
-    xv[it] = cnt == 2 ? 0.5 * sum : sum;
+    xv[it] = vertex_derivative_from_ends<N>(
+        v < K, v > 0, k, [&](int j) { return co[((bl * K + v) * D + d) * N + j]; },
+        [&](int j) { return (co + ((bl * K + v - 1) * D + d) * N)[j]; }, [&]() { return tl[bl * K + v - 1]; });
   }
   __syncthreads();
   double* dst = values + b0 * xsz;

@@ -1,5 +1,8 @@
-// mtg_vertex_common.h -- coefficients of one (segment, dimension) from the derivatives at its two
-// ends, shared by mtg_vertex.hip (mtg_coefficients_from_vertices_batch) and mtg_soft_constraint.hip:
+// mtg_vertex_common.h -- the per-item arithmetic of the two vertex <-> coefficient maps, shared by the
+// uniform kernels (mtg_vertex.hip), the CSR kernels (mtg_vertex_ragged.hip) and mtg_soft_constraint.hip,
+// so that an item's bits do not depend on the kernel that computes it.
+//
+// coefficients_from_ends: coefficients of one (segment, dimension) from the derivatives at its two ends,
 // c = A(T)^-1 [x_i; x_{i+1}], the reference's updateSegmentsFromCompactConstraints (lin_impl:253-273),
 // with A(T)^-1 = diag(T^-j) A(1)^-1 S(T) from the exact-rational A(1)^-1 table and the segment's start
 // position subtracted first (only c_0 changes; no cancellation of p_i against p_{i+1} in c_j, j >= h).
@@ -41,6 +44,56 @@ __device__ __forceinline__ void coefficients_from_ends(XEnd xend, double T, doub
     }
     out[j] = acc * tp;
     tp *= tinv;
+  }
+}
+
+// falling factorial k!/(k-n)! (Polynomial::base_coefficients_, src/polynomial.cpp:140-155)
+__device__ __forceinline__ double falling(int k, int n) {
+  double f = 1.0;
+  for (int q = 0; q < n; ++q) f *= (double)(k - q);
+  return f;
+}
+
+// vertex_derivative_from_ends: derivative k of one dimension at one vertex, the reference's M^+ A p
+// (nl_impl:162-180): the mean of the two segment ends that meet at an interior vertex, the single end at
+// the first / last vertex of a trajectory.  cstart(j): coefficient j of the segment that starts at the
+// vertex (called when at_start); cend(j) and tend(): coefficient j and the time of the segment that ends
+// there (called when at_end).  At least one of the two holds.
+template <int N, class CStart, class CEnd, class TEnd>
+__device__ __forceinline__ double vertex_derivative_from_ends(bool at_start, bool at_end, int k, CStart cstart,
+                                                              CEnd cend, TEnd tend) {
+  double sum = 0.0;
+  int cnt = 0;
+  if (at_start) {  // start of the segment: p^(k)(0) = k! c_k
+    sum += falling(k, k) * cstart(k);
+    ++cnt;
+  }
+  if (at_end) {  // end of the segment before: p^(k)(T) = sum_j j!/(j-k)! c_j T^(j-k)  (Horner)
+    const double T = tend();
+    double acc = 0.0;
+    for (int j = N - 1; j >= k; --j) acc = acc * T + falling(j, k) * cend(j);
+    sum += acc;
+    ++cnt;
+  }
+  return cnt == 2 ? 0.5 * sum : sum;
+}
+
+// dst[i] = src[i] for i < n by a block of kVtxThreads, U loads per thread in flight before the stores.
+constexpr int kVtxThreads = 256;
+template <int U>
+__device__ __forceinline__ void stage_copy(const double* __restrict__ src, double* dst, int n, int tid) {
+  for (int base = 0; base < n; base += U * kVtxThreads) {
+    double r[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = base + u * kVtxThreads + tid;
+      r[u] = src[i < n ? i : n - 1];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = base + u * kVtxThreads + tid;
+      if (i < n) dst[i] = r[u];
+    }
   }
 }
 

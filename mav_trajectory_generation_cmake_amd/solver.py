@@ -540,6 +540,94 @@ class Context:
                                                          _addr(out), 0), self.handle)
         return out
 
+    def vertex_derivatives_ragged_batch(self, coeffs, times, seg_count, asynchronous=False):
+        """vertex_derivatives_batch for a batch of different segment counts
+        (mtg_vertex_derivatives_ragged_batch): coeffs [sum K][D][N] and times [sum K] are the CSR arrays
+        Context.solve_linear_ragged_batch returns and takes (numpy or torch-device), seg_count [B] a host
+        array either way.  Returns vertex_values [sum K + B][N/2][D] (split_ragged kind "vertex_values");
+        every trajectory's rows are the bytes vertex_derivatives_batch gives for it alone, and there is no
+        limit on K."""
+        coeffs, times = _csr(coeffs), _csr(times)
+        seg_count, B, D, N = _ragged_coeff_shape(coeffs, times, seg_count)
+        shape = (int(coeffs.shape[0]) + B, N // 2, D)
+        coeffs, times, out, flags = self._ragged_map_arrays(coeffs, times, shape, asynchronous)
+        nat.check(self._lib.mtg_vertex_derivatives_ragged_batch(self.handle, N, D, B, _addr(seg_count), _addr(coeffs),
+                                                                _addr(times), _addr(out), flags), self.handle)
+        return out
+
+    def coefficients_from_vertices_ragged_batch(self, N, vertex_values, times, seg_count, asynchronous=False):
+        """coefficients_from_vertices_batch for a batch of different segment counts
+        (mtg_coefficients_from_vertices_ragged_batch): vertex_values [sum K + B][N/2][D] (all derivatives)
+        and times [sum K], numpy or torch-device; seg_count [B] a host array.  Returns coeffs [sum K][D][N];
+        every trajectory's block is the bytes coefficients_from_vertices_batch gives for it alone."""
+        vertex_values, times = _csr(vertex_values), _csr(times)
+        seg_count, B, D = _ragged_vertex_shape(N, vertex_values, times, seg_count)
+        shape = (int(times.shape[0]), D, N)
+        vertex_values, times, out, flags = self._ragged_map_arrays(vertex_values, times, shape, asynchronous)
+        nat.check(self._lib.mtg_coefficients_from_vertices_ragged_batch(self.handle, N, D, B, _addr(seg_count),
+                                                                        _addr(vertex_values), _addr(times), _addr(out),
+                                                                        flags), self.handle)
+        return out
+
+    def _ragged_map_arrays(self, a, times, out_shape, asynchronous):
+        """The contiguous inputs, the output array and the flags of a ragged vertex-map call."""
+        if _is_torch(a) and a.is_cuda:
+            import torch
+            out = torch.empty(out_shape, dtype=torch.float64, device=a.device)
+            self.set_stream(torch.cuda.current_stream(a.device).cuda_stream)
+            return a.contiguous(), times.contiguous(), out, nat.MTG_FLAG_DEVICE_PTRS | (nat.MTG_FLAG_ASYNC if asynchronous else 0)
+        self.reset_stream()
+        return (np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(times, dtype=np.float64),
+                np.empty(out_shape), 0)
+
+    def collision_cost_ragged_batch(self, N, vertex_values, times, seg_count, grid, params, mask=None, grad=False,
+                                    asynchronous=False):
+        """collision_cost_batch for a batch of different segment counts (mtg_collision_cost_ragged_batch):
+        vertex_values [sum K + B][N/2][3] (all derivatives), mask [sum K + B] and times [sum K] are CSR arrays
+        (numpy, or torch-device with a torch grid.distance), seg_count [B] a host array either way.  Returns
+        dict(cost, collision, n_evaluated, status), each [B], and with grad=True (needs mask) grad, flat
+        3 N/2 (sum K + B) doubles in the layout of solve_linear_ragged_batch's free (split_ragged kind
+        "grad").  Every trajectory's outputs are the bytes collision_cost_batch gives for it alone."""
+        vertex_values, times = _csr(vertex_values), _csr(times)
+        dev = _is_torch(vertex_values) and vertex_values.is_cuda
+        seg_count, B, D = _ragged_vertex_shape(N, vertex_values, times, seg_count)
+        totV, h = int(vertex_values.shape[0]), N // 2
+        assert not grad or mask is not None, "grad needs mask"
+        assert mask is None or tuple(mask.shape) == (totV,), "mask must be [sum K + B]"
+        if dev:
+            import torch
+            assert _is_torch(grid.distance) and grid.distance.is_cuda, "device call: grid.distance must be a CUDA tensor"
+            kw = dict(device=vertex_values.device)
+            vertex_values, times = vertex_values.contiguous(), times.contiguous()
+            mask = mask.contiguous() if mask is not None else None
+            out = {"cost": torch.empty(B, dtype=torch.float64, **kw),
+                   "collision": torch.empty(B, dtype=torch.uint8, **kw),
+                   "n_evaluated": torch.empty(B, dtype=torch.int32, **kw),
+                   "status": torch.empty(B, dtype=torch.int32, **kw)}
+            if grad:
+                out["grad"] = torch.empty((totV * h * D,), dtype=torch.float64, **kw)
+            flags = nat.MTG_FLAG_DEVICE_PTRS | (nat.MTG_FLAG_ASYNC if asynchronous else 0)
+            self.set_stream(torch.cuda.current_stream(vertex_values.device).cuda_stream)
+        else:
+            vertex_values = np.ascontiguousarray(vertex_values, dtype=np.float64)
+            times = np.ascontiguousarray(times, dtype=np.float64)
+            mask = np.ascontiguousarray(mask, dtype=np.uint8) if mask is not None else None
+            out = {"cost": np.empty(B), "collision": np.empty(B, np.uint8), "n_evaluated": np.empty(B, np.int32),
+                   "status": np.empty(B, np.int32)}
+            if grad:
+                out["grad"] = np.zeros((totV * h * D,))
+            flags = 0
+            self.reset_stream()
+        g, keep = grid.native()
+        nat.check(self._lib.mtg_collision_cost_ragged_batch(self.handle, N, D, B, _addr(seg_count), _addr(vertex_values),
+                                                            _addr(mask) if grad else None, _addr(times), ctypes.byref(g),
+                                                            ctypes.byref(params.native()), _addr(out["cost"]),
+                                                            _addr(out.get("grad")), _addr(out["collision"]),
+                                                            _addr(out["n_evaluated"]), _addr(out["status"]), flags),
+                  self.handle)
+        del keep
+        return out
+
     def set_free_constraints_batch(self, N, values, mask, times, free):
         """PolynomialOptimization::setFreeConstraints (polynomial_optimization_linear.h:185-186) for a
         batch: the fixed values stay, the free derivatives come from `free` [B][D][V*h] (reference
@@ -948,6 +1036,16 @@ def _ragged_coeff_shape(coeffs, times, seg_count):
     assert coeffs.ndim == 3 and int(coeffs.shape[0]) == totS, "coeffs must be [sum K][D][N]"
     assert tuple(times.shape) == (totS,), "times must be [sum K]"
     return seg_count, int(seg_count.shape[0]), int(coeffs.shape[1]), int(coeffs.shape[2])
+
+
+def _ragged_vertex_shape(N, vertex_values, times, seg_count):
+    """(seg_count as int32, B, D) of the CSR arrays vertex_values [sum K + B][N/2][D], times [sum K]."""
+    seg_count = np.ascontiguousarray(seg_count, dtype=np.int32).reshape(-1)
+    B, totS = int(seg_count.shape[0]), int(seg_count.sum(dtype=np.int64))
+    assert vertex_values.ndim == 3 and int(vertex_values.shape[0]) == totS + B and int(vertex_values.shape[1]) == N // 2, \
+        "vertex_values must be [sum K + B][N/2][D]"
+    assert tuple(times.shape) == (totS,), "times must be [sum K]"
+    return seg_count, B, int(vertex_values.shape[2])
 
 
 def _query_rows(t_query, B, strides, contiguous):
@@ -1572,20 +1670,24 @@ def pack_ragged(problems):
 
 
 _RAGGED_KINDS = {"values": "vertex", "mask": "vertex", "times": "segment", "coeffs": "segment", "free": "free",
-                 "n_free": "trajectory", "cost": "trajectory", "status": "trajectory"}
+                 "n_free": "trajectory", "cost": "trajectory", "status": "trajectory",
+                 # the ragged vertex maps and collision cost: all vertex derivatives, the gradient block (free's
+                 # layout), and the collision entry's per-trajectory outputs
+                 "vertex_values": "vertex", "grad": "free", "collision": "trajectory", "n_evaluated": "trajectory"}
 
 
 def split_ragged(array, seg_count, kind, D=None):
     """Per-trajectory views (no copies) of one CSR array of a ragged batch, numpy or torch.  kind names
     the array: "values" -> [V_b][N/2][D], "mask" -> [V_b], "times" -> [K_b], "coeffs" -> [K_b][D][N],
-    "free" -> [D][V_b N/2] (needs D), "n_free" / "cost" / "status" -> the entry of b."""
+    "free" -> [D][V_b N/2] (needs D), "n_free" / "cost" / "status" -> the entry of b; "vertex_values" as
+    "values", "grad" (collision_cost_ragged_batch) as "free", "collision" / "n_evaluated" as "cost"."""
     what = _RAGGED_KINDS[kind]
     vo, so = ragged_offsets(seg_count)
     B = len(vo) - 1
     if what == "trajectory":
         return [array[b] for b in range(B)]
     if what == "free":
-        assert D is not None, "split_ragged(..., 'free') needs D"
+        assert D is not None, "split_ragged(..., '%s') needs D" % kind
         flat = array.reshape(-1)
         hD = int(flat.shape[0]) // max(int(vo[-1]), 1)
         return [flat[hD * int(vo[b]):hD * int(vo[b + 1])].reshape(D, -1) for b in range(B)]
@@ -1675,6 +1777,69 @@ def host_min_max_magnitude_ragged_batch(coeffs, times, seg_count, derivative, di
                                                                  int(derivative), mask, _addr(mn), _addr(mx),
                                                                  int(threads)))
     return mn, mx
+
+
+def host_vertex_derivatives_batch(coeffs, times, threads=1):
+    """Context.vertex_derivatives_batch on the library's host path (mtg_host_vertex_derivatives_batch): scalar
+    C++, no GPU, any K.  coeffs [B][K][D][N], times [B][K] -> [B][K + 1][N/2][D]."""
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    B, K, D, N = coeffs.shape
+    assert times.shape == (B, K)
+    out = np.empty((B, K + 1, N // 2, D))
+    nat.check(nat.load().mtg_host_vertex_derivatives_batch(N, D, K, B, _addr(coeffs), _addr(times), _addr(out),
+                                                           int(threads)))
+    return out
+
+
+def host_vertex_derivatives_ragged_batch(coeffs, times, seg_count, threads=1):
+    """Context.vertex_derivatives_ragged_batch on the library's host path
+    (mtg_host_vertex_derivatives_ragged_batch): no GPU; every trajectory's rows are the bytes
+    host_vertex_derivatives_batch gives for it alone.  numpy CSR arrays (or lists of per-trajectory blocks)."""
+    coeffs = np.ascontiguousarray(_csr(coeffs), dtype=np.float64)
+    times = np.ascontiguousarray(_csr(times), dtype=np.float64)
+    seg_count, B, D, N = _ragged_coeff_shape(coeffs, times, seg_count)
+    out = np.empty((coeffs.shape[0] + B, N // 2, D))
+    nat.check(nat.load().mtg_host_vertex_derivatives_ragged_batch(N, D, B, _addr(seg_count), _addr(coeffs), _addr(times),
+                                                                  _addr(out), int(threads)))
+    return out
+
+
+def host_coefficients_from_vertices_ragged_batch(N, vertex_values, times, seg_count, threads=1):
+    """Context.coefficients_from_vertices_ragged_batch on the library's host path
+    (mtg_host_coefficients_from_vertices_ragged_batch): no GPU; every trajectory's block is the bytes
+    mtg_host_coefficients_from_vertices_batch gives for it alone.  numpy CSR arrays (or lists of blocks)."""
+    vertex_values = np.ascontiguousarray(_csr(vertex_values), dtype=np.float64)
+    times = np.ascontiguousarray(_csr(times), dtype=np.float64)
+    seg_count, B, D = _ragged_vertex_shape(N, vertex_values, times, seg_count)
+    out = np.empty((times.shape[0], D, N))
+    nat.check(nat.load().mtg_host_coefficients_from_vertices_ragged_batch(N, D, B, _addr(seg_count), _addr(vertex_values),
+                                                                          _addr(times), _addr(out), int(threads)))
+    return out
+
+
+def host_collision_cost_ragged_batch(N, vertex_values, times, seg_count, grid, params, mask=None, grad=False, threads=1):
+    """Context.collision_cost_ragged_batch on the library's host path (mtg_host_collision_cost_ragged_batch): no
+    GPU; every trajectory's outputs are the bytes host_collision_cost_batch gives for it alone.  Same arguments
+    (numpy CSR arrays) and outputs."""
+    vertex_values = np.ascontiguousarray(_csr(vertex_values), dtype=np.float64)
+    times = np.ascontiguousarray(_csr(times), dtype=np.float64)
+    seg_count, B, D = _ragged_vertex_shape(N, vertex_values, times, seg_count)
+    totV, h = vertex_values.shape[0], N // 2
+    assert not grad or mask is not None, "grad needs mask"
+    mask = np.ascontiguousarray(mask, dtype=np.uint8) if mask is not None else None
+    assert mask is None or mask.shape == (totV,), "mask must be [sum K + B]"
+    out = {"cost": np.empty(B), "collision": np.empty(B, np.uint8), "n_evaluated": np.empty(B, np.int32),
+           "status": np.empty(B, np.int32)}
+    if grad:
+        out["grad"] = np.zeros((totV * h * D,))
+    g, keep = grid.native()
+    nat.check(nat.load().mtg_host_collision_cost_ragged_batch(
+        N, D, B, _addr(seg_count), _addr(vertex_values), _addr(mask) if grad else None, _addr(times), ctypes.byref(g),
+        ctypes.byref(params.native()), _addr(out["cost"]), _addr(out.get("grad")), _addr(out["collision"]),
+        _addr(out["n_evaluated"]), _addr(out["status"]), int(threads)))
+    del keep
+    return out
 
 
 # ----------------------------------------------------------------- generators
