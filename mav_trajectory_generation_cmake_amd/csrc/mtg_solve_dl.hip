@@ -34,3 +34,31 @@ hipError_t launch_solve_dl(int N, const SolveArgs& a, hipStream_t stream) {
 }
 
 }  // namespace mtg
+
+// The hot header (DlHot, 64 bytes into `out`) the launcher fills for a launch of these arguments: a
+// host-only hook for the tests (tests/test_dl_header.py), not part of the C ABI (include/mtg.h).
+// Returns 0, or -1 where the DL kernel does not serve the shape.
+extern "C" int mtgtest_dl_hot_header(int N, int D, int K, int r, const void* values, const void* mask, const void* times,
+                                     void* coeffs, const void* scales, int64_t B, int n_cand, int any_optional,
+                                     void* out) {
+  using namespace mtg;
+  if (!dl_geometry(N, D, K, r) || B < 1) return -1;
+  SolveArgs a{};
+  a.values = static_cast<const double*>(values);
+  a.mask = static_cast<const uint8_t*>(mask);
+  a.times = static_cast<const double*>(times);
+  a.coeffs = static_cast<double*>(coeffs);
+  a.scales = static_cast<const double*>(scales);
+  static int32_t dummy_status;  // (the fill only tests the optional outputs against null)
+  a.status = any_optional ? &dummy_status : nullptr;
+  a.B = B;
+  a.K = K;
+  a.D = D;
+  a.r = r;
+  a.n_cand = n_cand;
+  const int tpw = kBlock / (2 * D);  // DlShape::TPW
+  DlHot h;
+  if (!dl_fill_hot(N, K, D, tpw, a, &h)) return -1;
+  *static_cast<DlHot*>(out) = h;  // (the caller's buffer: 64 bytes, 8-byte aligned)
+  return 0;
+}

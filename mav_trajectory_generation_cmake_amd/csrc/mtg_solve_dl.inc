@@ -170,15 +170,20 @@ struct DlPow {
 // pinned (factor_pins), so vertex 1's Schur product and the backward solve at vertex 0 skip them; the
 // interior steps are the pattern's.  (With the generators' pins it is the long-chain pattern pass
 // exactly, bit for bit: the masked terms it adds are exact zeros.)
+//
+// ST (status): the chain keeps what the status is made of -- the smallest pivot (pivot_min in the
+// factorisations' dependent chain) and, for long chains, the parked times' status bits.  A launch that
+// asks for no status, cost or n_free (DlHot, launch_dl_nrk) runs ST = false: the same f64 operations
+// on the solution's path, none of the checks.
 enum DlMode : int { kDlPattern = 0, kDlEnds = 1, kDlGeneral = 2 };
-template <int N, int R, int KMAX, int D, int MODE = kDlPattern>
+template <int N, int R, int KMAX, int D, int MODE = kDlPattern, bool ST = true>
 struct DlChain {
   using SH = DlShape<N, KMAX, D>;
   static constexpr bool G = MODE == kDlGeneral, EP = MODE == kDlEnds;
   static constexpr int H = SH::H, F = SH::F, KC = SH::KC, KS = SH::KS, NL = SH::NL, FS = SH::FS;
   static constexpr int PE = SH::PE, J0 = (G || EP) ? 0 : SH::J0;
   static constexpr int NN = N, RR_ = R, KM = KMAX, DD = D;
-  static constexpr bool GG = G, EE = EP;
+  static constexpr bool GG = G, EE = EP, SS = ST;
   static constexpr unsigned FM = (1u << F) - 1u;
   static constexpr bool RR = SH::RR;
   static constexpr int TOP = KS - 1;
@@ -251,8 +256,10 @@ struct DlChain {
     if constexpr (FR) {
       park[(J + 1) * kBlock] = Pf[J + 1];
       if (twr) tpark[J * tstride] = Tf[J];
-      tbits |= time_bits(Tf[J]) | dl_scale_bits<N, R>(Tf[J]);
-      asm volatile("" : "+v"(tbits));  // (taken here, not kept live to the end of the sweep)
+      if constexpr (ST) {
+        tbits |= time_bits(Tf[J]) | dl_scale_bits<N, R>(Tf[J]);
+        asm volatile("" : "+v"(tbits));  // (taken here, not kept live to the end of the sweep)
+      }
     }
   }
   // Every step reads the same table entries: without this the compiler hoists the entries all
@@ -316,11 +323,13 @@ struct DlChain {
         w[k] = S[j][k] * dg[k];
         dj -= S[j][k] * w[k];
       }
-      pmin = pivot_min(pmin, dj);
-      // (long chains: materialised here -- left to the compiler, every pivot of the sweep stayed live
-      // until the status was reduced at the end, 50 doubles at config 4, spilled to AGPRs and scratch;
-      // 29.3 -> 28.2 us.  Short chains are faster without it: 10.8 vs 11.1 us at config 2.)
-      if (RR) asm volatile("" : "+v"(pmin));
+      if constexpr (ST) {
+        pmin = pivot_min(pmin, dj);
+        // (long chains: materialised here -- left to the compiler, every pivot of the sweep stayed live
+        // until the status was reduced at the end, 50 doubles at config 4, spilled to AGPRs and scratch;
+        // 29.3 -> 28.2 us.  Short chains are faster without it: 10.8 vs 11.1 us at config 2.)
+        if (RR) asm volatile("" : "+v"(pmin));
+      }
       const double inv = rcp(dj);
       dg[j] = dj;
       dinv[j] = inv;
@@ -847,13 +856,23 @@ struct DlStore {
   }
 };
 
+// The outputs of a pass, as the pass takes them: the pattern pass's from the kernel's hot header
+// (DlHot) and, only where the launch asks for an optional one, from the arguments behind it.
+struct DlOuts {
+  double* coeffs;
+  double* free_out;
+  double* cost_out;
+  int32_t* status;
+  int32_t* n_free_out;
+};
+
 // One backward round: y_J (bstep, or z'_0 at J = 0), segment J's coefficients staged in LDS and
 // written as the wave's runs (chain A's segment J and chain B's K-1-J of each trajectory), the free
 // values of chain vertex J, then y_J becomes the next round's Y.  own: this lane's trajectory is
 // valid and follows the pattern (its outputs are this kernel's to write).  FIRSTB: J == KC-1, whose
 // end vertex (the meeting vertex) is scaled with T_{KC-1} itself (rho = 1).
 template <typename DC, int AL16, bool FIRSTB = false>
-__device__ __forceinline__ void dl_round(DC& c, const SolveArgs& a, int J, int lane, int ch, int d, bool own, int64_t pb,
+__device__ __forceinline__ void dl_round(DC& c, const DlOuts& a, int J, int lane, int ch, int d, bool own, int64_t pb,
                                          double* stg, const DlStore<DC::NN, DC::KM, DC::DD, AL16>& sm,
                                          __amdgpu_buffer_rsrc_t out) {
   constexpr int N = DC::NN, KMAX = DC::KM, D = DC::DD;
@@ -896,7 +915,7 @@ __device__ __forceinline__ void dl_round(DC& c, const SolveArgs& a, int J, int l
     }
   }
   double occ[N];
-  c.segment_row(ch != 0, a.cost_out != nullptr, J, tinv, y, v, occ);
+  c.segment_row(ch != 0, DC::SS && a.cost_out != nullptr, J, tinv, y, v, occ);
   if (DC::GG && a.free_out && own) {
     // chain vertex J's free values in the reference's (vertex, derivative) order, at the offset of
     // its vertex among all vertices' free values
@@ -994,6 +1013,80 @@ __device__ __forceinline__ void dl_fallback(const SolveArgs& a, int64_t pair0, i
   }
 }
 
+// The kernel's only parameter: the hot header, then the full arguments.
+//
+// DlHot is everything a plain solve's pattern pass reads, in the kernarg segment's first 64 bytes, so
+// the wave's head is one s_load_dwordx16 and one wait before its input loads leave -- the fields used
+// to span two lines, the second read only after the first had been waited for and branched on.  What
+// is uniform over the launch is worked out once on the host (dl_fill_hot): the byte sizes of a full
+// wave's regions (a wave's base is blockIdx.x times one of them, a 32 x 32 -> 64-bit product), the
+// last wave's place and trajectory count instead of B, and the plain-solve decision instead of n_cand
+// and scales.  The time sweep (not kDlPlain) takes B, n_cand and scales from the arguments behind the
+// header, in a branch of its own: its 64-bit divisions stay off the plain path.
+//
+// The passes other than the pattern's re-read the parameter from the kernarg segment (dl_args): a
+// reference to the kernel's parameter would make the kernel copy it to the stack and read its fields
+// from there in the pattern pass too, and values shared with the pattern pass would be kept live
+// (SGPRs spilled to VGPR lanes) through it.  As the kernel's single explicit parameter it sits at
+// offset 0 of the kernarg segment, so the pointer below is its address.
+enum DlHotFlags : uint32_t {
+  kDlPlain = 1u,     // n_cand == 1 and no scales: pair p is trajectory p, times unscaled
+  kDlCoeffs = 2u,    // coeffs != null
+  kDlOptional = 4u,  // any of free_out, n_free_out, cost_out, status asked for
+};
+struct DlHot {
+  const double* values;
+  const uint8_t* mask;
+  const double* times;
+  double* coeffs;
+  uint32_t vbytes, mbytes, tbytes, obytes;  // bytes of tpw trajectories' values, masks, times, coefficients
+  int32_t tpw;                              // trajectories per wave (<= DlShape::TPW)
+  uint32_t flags;                           // DlHotFlags
+  uint32_t last_block;                      // the launch's last wave ...
+  int32_t last_nvt;                         // ... and its trajectories (pairs), 1..tpw
+};
+static_assert(sizeof(DlHot) == 64, "the hot header is one 64-byte line");
+struct DlKernArgs {
+  DlHot h;
+  SolveArgs a;
+};
+static_assert(offsetof(DlKernArgs, h) == 0, "the hot header leads the kernarg segment");
+__device__ __forceinline__ const DlKernArgs& dl_args() {
+  return *reinterpret_cast<const DlKernArgs*>((uintptr_t)__builtin_amdgcn_kernarg_segment_ptr());
+}
+// The hot header as one 64-byte scalar load, materialised whole: left to the compiler, the fields are
+// loaded in pieces where each is first used, each piece with a wait of its own.
+__device__ __forceinline__ DlHot dl_hot() {
+  typedef uint32_t dl_u32x16 __attribute__((ext_vector_type(16)));
+  dl_u32x16 v = *(const __attribute__((address_space(4))) dl_u32x16*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(v));
+  return __builtin_bit_cast(DlHot, v);
+}
+
+// The header of a launch of B pairs in waves of tpw (host; restated in tests/test_dl_header.py).
+// False if a wave's region would not fit 32 bits (no shape the kernel is built for comes near).
+inline bool dl_fill_hot(int N, int K, int D, int tpw, const SolveArgs& a, DlHot* h) {
+  const int64_t V = K + 1, H = N / 2;
+  const int64_t vb = tpw * V * H * D * 8, mb = tpw * V, tb = (int64_t)tpw * K * 8, ob = (int64_t)tpw * K * D * N * 8;
+  if (a.B < 1 || tpw < 1 || vb > INT32_MAX || ob > INT32_MAX) return false;
+  const int64_t blocks = (a.B + tpw - 1) / tpw;
+  if (blocks > UINT32_MAX) return false;
+  h->values = a.values;
+  h->mask = a.mask;
+  h->times = a.times;
+  h->coeffs = a.coeffs;
+  h->vbytes = (uint32_t)vb;
+  h->mbytes = (uint32_t)mb;
+  h->tbytes = (uint32_t)tb;
+  h->obytes = (uint32_t)ob;
+  h->tpw = tpw;
+  h->flags = (a.n_cand == 1 && !a.scales ? kDlPlain : 0u) | (a.coeffs ? kDlCoeffs : 0u) |
+             (a.free_out || a.n_free_out || a.cost_out || a.status ? kDlOptional : 0u);
+  h->last_block = (uint32_t)(blocks - 1);
+  h->last_nvt = (int32_t)(a.B - (blocks - 1) * tpw);
+  return true;
+}
+
 // The wave's and this lane's place in the batch, and the buffer resources of the wave's inputs (one
 // trajectory per 2 D lanes: lane t 2D + ch D + d is trajectory t, chain ch, dimension d).
 template <int N, int KMAX, int D>
@@ -1005,8 +1098,11 @@ struct DlWave {
   int64_t pair0, pb;
   double tscale;
   __amdgpu_buffer_rsrc_t rv, rt, rm;
+  const char* obase;           // the wave's coefficients (the values where none are asked for: never stored to)
   int vo, vs, to, ts, mo, ms;  // this lane's first vertex / time / mask and the strides of its chain (bytes)
-  __device__ __forceinline__ DlWave(const SolveArgs& a, int tpw, int lane_id) {
+  // h: the hot header (dl_hot); a: the full arguments behind it (read by a time sweep only)
+  __device__ __forceinline__ DlWave(const DlHot& h, const SolveArgs& a, int lane_id) {
+    const int tpw = h.tpw;
     lane = lane_id;
     t = lane / (2 * D);
     r2 = lane - t * (2 * D);
@@ -1014,22 +1110,31 @@ struct DlWave {
     d = r2 - ch * D;
     tq = t < SH::TPW ? t : 0;
     partner = ch ? lane - D : lane + D;
-    pair0 = (int64_t)blockIdx.x * tpw;
-    const int64_t pair = pair0 + t;
-    valid = t < tpw && pair < a.B;
-    pb = valid ? pair : pair0;
-    nvt = (int)(a.B - pair0 < tpw ? a.B - pair0 : tpw);  // the wave's trajectories
-    // the wave's problems (trajectories; for a time sweep, pair pb solves trajectory pb / n_cand) as
-    // buffer resources from its first one on, addressed with 32-bit lane offsets
-    const int64_t nc = a.n_cand;
-    const int64_t tr0 = nc == 1 ? pair0 : pair0 / nc;
-    trl = (int)((nc == 1 ? pb : pb / nc) - tr0);
-    const int64_t ntr = nc == 1 ? a.B : (a.B + nc - 1) / nc;
-    const int ntw = (int)(ntr - tr0 < SH::TPW ? ntr - tr0 : SH::TPW);
-    rv = dl_rsrc(a.values + tr0 * (V * H * D), (uint32_t)(ntw * V * H * D * 8));
-    rt = dl_rsrc(a.times + tr0 * K, (uint32_t)(ntw * K * 8));
-    rm = dl_rsrc(a.mask + tr0 * V, (uint32_t)(ntw * V));
-    tscale = a.scales ? a.scales[pb % nc] : 1.0;
+    const uint32_t bid = blockIdx.x;
+    nvt = bid == h.last_block ? h.last_nvt : tpw;  // the wave's trajectories
+    pair0 = (int64_t)((uint64_t)bid * (uint32_t)tpw);
+    valid = t < nvt;
+    pb = valid ? pair0 + t : pair0;
+    obase = (h.flags & kDlCoeffs) ? reinterpret_cast<const char*>(h.coeffs) + (uint64_t)bid * h.obytes
+                                  : reinterpret_cast<const char*>(h.values);
+    // the wave's problems as buffer resources from its first one on, addressed with 32-bit lane offsets
+    if (__builtin_expect((h.flags & kDlPlain) != 0u, 1)) {
+      trl = valid ? t : 0;
+      rv = dl_rsrc(reinterpret_cast<const char*>(h.values) + (uint64_t)bid * h.vbytes, (uint32_t)(nvt * (V * H * D * 8)));
+      rt = dl_rsrc(reinterpret_cast<const char*>(h.times) + (uint64_t)bid * h.tbytes, (uint32_t)(nvt * (K * 8)));
+      rm = dl_rsrc(h.mask + (uint64_t)bid * h.mbytes, (uint32_t)(nvt * V));
+      tscale = 1.0;
+    } else {  // a time sweep: pair pb solves trajectory pb / n_cand with its times scaled
+      const int64_t nc = a.n_cand;
+      const int64_t tr0 = pair0 / nc;
+      trl = (int)(pb / nc - tr0);
+      const int64_t ntr = (a.B + nc - 1) / nc;
+      const int ntw = (int)(ntr - tr0 < SH::TPW ? ntr - tr0 : SH::TPW);
+      rv = dl_rsrc(a.values + tr0 * (V * H * D), (uint32_t)(ntw * V * H * D * 8));
+      rt = dl_rsrc(a.times + tr0 * K, (uint32_t)(ntw * K * 8));
+      rm = dl_rsrc(a.mask + tr0 * V, (uint32_t)(ntw * V));
+      tscale = a.scales ? a.scales[pb % nc] : 1.0;
+    }
     // (chain B walks the vertices backwards)
     vo = (trl * (V * H * D) + (ch ? K * H * D : 0) + d) * 8;
     vs = ch ? -(H * D * 8) : H * D * 8;
@@ -1038,6 +1143,8 @@ struct DlWave {
     mo = trl * V + (ch ? K : 0);
     ms = ch ? -1 : 1;
   }
+  // the wave's coefficient runs ([nvt][K][D][N])
+  __device__ __forceinline__ __amdgpu_buffer_rsrc_t out() const { return dl_rsrc(obase, (uint32_t)(nvt * (K * D * N * 8))); }
   __device__ __forceinline__ unsigned mask(int j) const { return __builtin_amdgcn_raw_buffer_load_b8(rm, mo + j * ms, 0, 0); }
   __device__ __forceinline__ double time(int j, double sc) const {
     return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rt, to + j * ts, 0, 0)) * sc;
@@ -1047,17 +1154,10 @@ struct DlWave {
   }
 };
 
-// The kernel's only parameter.  The passes other than the pattern's re-read it from the kernarg
-// segment (dl_args): a reference to the kernel's parameter would make the kernel copy it to the stack
-// and read its fields from there in the pattern pass too, and values shared with the pattern pass
-// would be kept live (SGPRs spilled to VGPR lanes) through it.  As the kernel's single explicit
-// parameter it sits at offset 0 of the kernarg segment, so the pointer below is its address.
-struct DlKernArgs {
-  SolveArgs a;
-  int tpw;  // trajectories per wave (<= DlShape::TPW)
-};
-__device__ __forceinline__ const DlKernArgs& dl_args() {
-  return *reinterpret_cast<const DlKernArgs*>((uintptr_t)__builtin_amdgcn_kernarg_segment_ptr());
+// A pass's outputs from the full arguments (the cold passes; the pattern pass of a launch that asks
+// for an optional output)
+__device__ __forceinline__ DlOuts dl_outs(const SolveArgs& a) {
+  return DlOuts{a.coeffs, a.free_out, a.cost_out, a.status, a.n_free_out};
 }
 
 // Status bits of the chain's segment times (time_bits, dl_scale_bits), materialised where they are
@@ -1079,7 +1179,7 @@ __device__ __forceinline__ int dl_time_bits(const double (&Tc)[KC]) {
 // dl_time_bits -- and dropped orders).  E: the end vertex's derivatives 1..F (the pattern and ends
 // passes; chain coordinates).  tph: the debug build's phase stamps.
 template <typename CC, int AL16, typename W>
-__device__ __forceinline__ void dl_run_pass(CC& cc, const SolveArgs& a, const W& w, const double (&E)[CC::F], bool mine,
+__device__ __forceinline__ void dl_run_pass(CC& cc, const DlOuts& a, const W& w, const double (&E)[CC::F], bool mine,
                                             int st, double* lds, uint64_t* tph) {
   constexpr int N = CC::NN, R = CC::RR_, KMAX = CC::KM, D = CC::DD;
   using SH = DlShape<N, KMAX, D>;
@@ -1096,8 +1196,8 @@ __device__ __forceinline__ void dl_run_pass(CC& cc, const SolveArgs& a, const W&
   MTG_DL_PSTAMP(2);
   // (times in registers: their status bits here, after the sweep -- taken before it, they would make
   // the sweep wait for the last segment time's load, where it now starts on the first vertex's)
-  if constexpr (CC::PR) st |= dl_time_bits<N, R, KC>(cc.Tr);
-  if constexpr (CC::FR) st |= cc.tbits;
+  if constexpr (CC::SS && CC::PR) st |= dl_time_bits<N, R, KC>(cc.Tr);
+  if constexpr (CC::SS && CC::FR) st |= cc.tbits;
   if (a.free_out && mine && ch == 0) {  // the meeting vertex, free values unscaled
     double* fo = a.free_out + (pb * D + d) * ((int64_t)V * H);
     if constexpr (CC::GG) {
@@ -1118,8 +1218,7 @@ __device__ __forceinline__ void dl_run_pass(CC& cc, const SolveArgs& a, const W&
   double* stg = lds + SH::STG_OFF;
   DlStore<N, KMAX, D, AL16> sm;
   sm.init(lane, w.nvt, __builtin_amdgcn_ballot_w64(!mine));
-  const __amdgpu_buffer_rsrc_t ro =
-      dl_rsrc(a.coeffs ? a.coeffs + w.pair0 * (int64_t)(K * D * N) : a.values, (uint32_t)(w.nvt * K * D * N * 8));
+  const __amdgpu_buffer_rsrc_t ro = w.out();
   dl_round<CC, AL16, true>(cc, a, KC - 1, lane, ch, d, mine, pb, stg, sm, ro);
 #pragma unroll
   for (int J = KC - 2; J >= 1; --J) {
@@ -1131,28 +1230,31 @@ __device__ __forceinline__ void dl_run_pass(CC& cc, const SolveArgs& a, const W&
   MTG_DL_PSTAMP(3);
 
   // ---- per trajectory: status (both chains, all dimensions) and the cost (sum over its 2 D lanes)
-  if (!(cc.pmin > 0.0 && cc.pmin <= DBL_MAX)) st |= MTG_TRAJ_NOT_SPD;
-  if (a.status || a.cost_out) {
-    double* red = lds + SH::RED_OFF;
-    int* redi = reinterpret_cast<int*>(red + kBlock);
-    __syncthreads();
-    red[lane] = cc.cacc;
-    redi[lane] = st;
-    __syncthreads();
-    if (w.r2 == 0 && mine) {
-      double cost = 0.0;
-      int s = 0;
+  // (ST = false: the launch asked for none of them)
+  if constexpr (CC::SS) {
+    if (!(cc.pmin > 0.0 && cc.pmin <= DBL_MAX)) st |= MTG_TRAJ_NOT_SPD;
+    if (a.status || a.cost_out) {
+      double* red = lds + SH::RED_OFF;
+      int* redi = reinterpret_cast<int*>(red + kBlock);
+      __syncthreads();
+      red[lane] = cc.cacc;
+      redi[lane] = st;
+      __syncthreads();
+      if (w.r2 == 0 && mine) {
+        double cost = 0.0;
+        int s = 0;
 #pragma unroll
-      for (int q = 0; q < 2 * D; ++q) cost += red[lane + q], s |= redi[lane + q];
-      if (a.cost_out) a.cost_out[pb] = cost;
-      if (a.status) a.status[pb] = s;
+        for (int q = 0; q < 2 * D; ++q) cost += red[lane + q], s |= redi[lane + q];
+        if (a.cost_out) a.cost_out[pb] = cost;
+        if (a.status) a.status[pb] = s;
+      }
     }
-  }
-  if (w.r2 == 0 && mine && a.n_free_out) {
-    if constexpr (CC::GG || CC::EE) {
-      a.n_free_out[pb] = cc.ftot;
-    } else {
-      a.n_free_out[pb] = SH::N_FREE(K);
+    if (w.r2 == 0 && mine && a.n_free_out) {
+      if constexpr (CC::GG || CC::EE) {
+        a.n_free_out[pb] = cc.ftot;
+      } else {
+        a.n_free_out[pb] = SH::N_FREE(K);
+      }
     }
   }
 #ifdef MTG_PHASE_TIMING
@@ -1212,11 +1314,12 @@ __device__ __forceinline__ void dl_take_inputs(CC& c, const double (&P)[CC::KC +
 // above N/2 - 1 dropped with WARN_DROPPED, lin_impl:74-95).  It re-reads its inputs (from L2, with a
 // laundered lane id) instead of taking them from the pattern pass, so nothing stays live across that
 // pass; in a cold branch, so the register allocator puts any spills here, not in the pattern pass.
-template <int N, int R, int KMAX, int D, int AL16>
+template <int N, int R, int KMAX, int D, int AL16, bool ST>
 __device__ __forceinline__ void dl_ends_pass(bool eown) {
   const DlKernArgs& ka = dl_args();
-  const SolveArgs a = ka.a;
-  const int tpw = ka.tpw;
+  const DlOuts a = dl_outs(ka.a);
+  const DlHot h = dl_hot();
+  const int tpw = h.tpw;
 #ifdef MTG_PHASE_TIMING  // (debug build: this pass's stamps, written like the pattern pass's)
   uint64_t tph[6];
   tph[0] = __builtin_amdgcn_s_memrealtime();
@@ -1224,13 +1327,13 @@ __device__ __forceinline__ void dl_ends_pass(bool eown) {
   uint64_t* tph = nullptr;
 #endif
   using SH = DlShape<N, KMAX, D>;
-  using EC = DlChain<N, R, KMAX, D, kDlEnds>;
+  using EC= DlChain<N, R, KMAX, D, kDlEnds, ST>;
   constexpr int H = N / 2, F = SH::F, KC = SH::KC;
   constexpr unsigned HM = (1u << H) - 1u;
   extern __shared__ __attribute__((aligned(16))) double lds[];
   int lane_id = threadIdx.x;
   asm volatile("" : "+v"(lane_id));
-  const DlWave<N, KMAX, D> w(a, tpw, lane_id);
+  const DlWave<N, KMAX, D> w(h, ka.a, lane_id);
   EC c;
   dl_place(c, w, tpw, lds);
   const unsigned m0 = w.mask(0);
@@ -1257,11 +1360,12 @@ __device__ __forceinline__ void dl_ends_pass(bool eown) {
 // The general-mask pass (DlChain<..., kDlGeneral>) for the wave's trajectories with gown set: every
 // position fixed, any other derivative at any vertex.  Like the ends pass it re-reads its inputs and
 // runs in a cold branch (it needs more registers than the pattern pass, and its spills go here).
-template <int N, int R, int KMAX, int D, int AL16>
+template <int N, int R, int KMAX, int D, int AL16, bool ST>
 __device__ __forceinline__ void dl_general_pass(bool gown) {
   const DlKernArgs& ka = dl_args();
-  const SolveArgs a = ka.a;
-  const int tpw = ka.tpw;
+  const DlOuts a = dl_outs(ka.a);
+  const DlHot h = dl_hot();
+  const int tpw = h.tpw;
 #ifdef MTG_PHASE_TIMING  // (debug build: this pass's stamps, written like the pattern pass's)
   uint64_t tph[6];
   tph[0] = __builtin_amdgcn_s_memrealtime();
@@ -1269,7 +1373,7 @@ __device__ __forceinline__ void dl_general_pass(bool gown) {
   uint64_t* tph = nullptr;
 #endif
   using SH = DlShape<N, KMAX, D>;
-  using DG = DlChain<N, R, KMAX, D, kDlGeneral>;
+  using DG= DlChain<N, R, KMAX, D, kDlGeneral, ST>;
   constexpr int H = N / 2, F = SH::F, KC = SH::KC;
   constexpr unsigned HM = (1u << H) - 1u;
   extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -1277,7 +1381,7 @@ __device__ __forceinline__ void dl_general_pass(bool gown) {
   // with the kernel's, they would stay live through the pattern pass)
   int lane_id = threadIdx.x;
   asm volatile("" : "+v"(lane_id));
-  const DlWave<N, KMAX, D> w(a, tpw, lane_id);
+  const DlWave<N, KMAX, D> w(h, ka.a, lane_id);
   DG g;
   dl_place(g, w, tpw, lds);
   g.rvals = w.rv;
@@ -1304,7 +1408,8 @@ __device__ __forceinline__ void dl_general_pass(bool gown) {
 #pragma unroll
     for (int j = 0; j < KC; ++j) g.tpark[j * g.tstride] = Tc[j];
   }
-  const int st0 = dl_time_bits<N, R, KC>(Tc) | (dropped ? MTG_TRAJ_WARN_DROPPED : 0);
+  int st0 = 0;
+  if constexpr (ST) st0 = dl_time_bits<N, R, KC>(Tc) | (dropped ? MTG_TRAJ_WARN_DROPPED : 0);
   int cs = 0;
 #pragma unroll
   for (int j = 0; j < KC; ++j) cs += g.nfv(j);
@@ -1327,15 +1432,33 @@ __device__ __forceinline__ void dl_general_pass(bool gown) {
 // general-mask DL pass (every vertex fixes its position), and the general kernel's block function
 // for the rest (a free position somewhere).  Which pass a trajectory takes depends on its own masks
 // only.
-template <int N, int R, int KMAX, int D, int AL16>
+// ST: the launch asks for status, cost or n_free (true), or for none of them (false: every pass runs
+// without the checks and the reduction that produce them -- DlChain).
+template <int N, int R, int KMAX, int D, int AL16, bool ST>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DlShape<N, KMAX, D>::WAVES))) void solve_dl_kernel(
     DlKernArgs ka) {  // (the single parameter: dl_args)
   using SH = DlShape<N, KMAX, D>;
-  using DC = DlChain<N, R, KMAX, D>;
+  using DC = DlChain<N, R, KMAX, D, kDlPattern, ST>;
   constexpr int F = SH::F, KC = SH::KC;
   constexpr unsigned EM = (1u << (SH::PE + 1)) - 1u;  // the end vertices' mask
-  const SolveArgs& a = ka.a;
-  const int tpw = ka.tpw;
+  const DlHot h = dl_hot();
+  const int tpw = h.tpw;
+  // the pattern pass's outputs: the coefficients from the header, the optional ones read only where
+  // the header says one is asked for
+  DlOuts a{h.coeffs, nullptr, nullptr, nullptr, nullptr};
+  if (h.flags & kDlOptional) {
+    // (the address laundered inside the branch: a plain kernarg load would be hoisted out of it)
+    typedef const __attribute__((address_space(4))) char* dl_kptr;  // (constant address space: scalar loads)
+    auto fa = (const __attribute__((address_space(4))) SolveArgs*)((dl_kptr)__builtin_amdgcn_kernarg_segment_ptr() +
+                                                                   offsetof(DlKernArgs, a));
+    asm volatile("" : "+s"(fa));
+    a.free_out = fa->free_out;
+    if constexpr (ST) {
+      a.cost_out = fa->cost_out;
+      a.status = fa->status;
+      a.n_free_out = fa->n_free_out;
+    }
+  }
   extern __shared__ __attribute__((aligned(16))) double lds[];
 #ifdef MTG_PHASE_TIMING  // (debug build: s_memrealtime stamps per wave, written over the first free values)
   uint64_t tph[6];
@@ -1343,7 +1466,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DlShape<
 #else
   uint64_t* tph = nullptr;
 #endif
-  const DlWave<N, KMAX, D> w(a, tpw, threadIdx.x);
+  const DlWave<N, KMAX, D> w(h, ka.a, threadIdx.x);
   const int t = w.t, d = w.d;
 
   DC c;
@@ -1412,15 +1535,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DlShape<
   // (cold for the register allocator: their spills go to these passes, not to the pattern's)
   if (__builtin_expect(__builtin_amdgcn_ballot_w64(eown) != 0, 0)) {
     __syncthreads();  // (the table copies; the pattern pass's LDS use before this pass's)
-    dl_ends_pass<N, R, KMAX, D, AL16>(eown);
+    dl_ends_pass<N, R, KMAX, D, AL16, ST>(eown);
   }
   if (__builtin_expect(__builtin_amdgcn_ballot_w64(gown) != 0, 0)) {
     __syncthreads();  // (the table copies; the previous passes' LDS use before this pass's)
-    dl_general_pass<N, R, KMAX, D, AL16>(gown);
+    dl_general_pass<N, R, KMAX, D, AL16, ST>(gown);
   }
   if (__builtin_expect(__builtin_amdgcn_ballot_w64(fown) != 0, 0)) {  // a free position somewhere: the general kernel's block
     __syncthreads();
-    dl_fallback<N, R, D>(a, w.pair0, w.nvt, __builtin_amdgcn_ballot_w64(fown), lds);
+    dl_fallback<N, R, D>(dl_args().a, w.pair0, w.nvt, __builtin_amdgcn_ballot_w64(fown), lds);
   }
 }
 // The chain lengths the kernel is built for (per N): config 2/3's and config 4's
@@ -1444,6 +1567,33 @@ inline bool dl_store_sc1(size_t bytes, bool long_chains) {
   return force >= 0 ? force == 1 : bytes <= ((size_t)(long_chains ? 192 : 64) << 20);
 }
 
+// Whether a launch that asks for no status, cost or n_free runs the status-free instantiation
+// (ST = false).  It is the shorter wave: where the launch lasts as long as one wave it gains (same box,
+// interleaved, profiles/dl_hot_header_ab.json: config 2 9.63 -> 9.49 us, config 4 23.48 -> 22.50 us),
+// but the HBM-bound config-3 shard (300 MB of coefficients, two waves per SIMD) ran 1 % slower with
+// it in five pairs of five (medians 92.3 -> 93.3 us).  So, like the sc1 store policy (dl_store_sc1), it is
+// chosen below the output size at which the launch turns HBM-bound -- the same bounds; the sizes
+// between the two measured regimes are not measured.  MTG_DL_STATUS=1 keeps the checks always, =0
+// drops them whenever nothing asks for them (A/B runs); read once per process.
+inline bool dl_status_free(size_t bytes, bool long_chains) {
+  static const int force = [] {
+    const char* v = getenv("MTG_DL_STATUS");
+    return v && (v[0] == '0' || v[0] == '1') ? v[0] - '0' : -1;
+  }();
+  return force >= 0 ? force == 0 : bytes <= ((size_t)(long_chains ? 192 : 64) << 20);
+}
+
+template <int N, int R, int KMAX, int D, int AL16, bool ST>
+static hipError_t launch_dl_inst(const DlKernArgs& ka, unsigned blocks, size_t lds, hipStream_t stream) {
+  if (lds > kMaxLdsPerBlock) {  // (long chains keep z' in LDS: beyond the default dynamic limit)
+    const hipError_t e = hipFuncSetAttribute((const void*)solve_dl_kernel<N, R, KMAX, D, AL16, ST>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  launch_kernel((solve_dl_kernel<N, R, KMAX, D, AL16, ST>), dim3(blocks), dim3(kBlock), lds, stream, ka);
+  return hipGetLastError();
+}
+
 template <int N, int R, int KMAX, int D>
 static hipError_t launch_dl_nrk(const SolveArgs& a, hipStream_t stream) {
   if constexpr (!DlShape<N, KMAX, D>::OK || R < 1) {
@@ -1452,25 +1602,26 @@ static hipError_t launch_dl_nrk(const SolveArgs& a, hipStream_t stream) {
     if (a.K != KMAX) return hipErrorInvalidValue;
     const size_t lds = dl_lds_bytes<N, D>(a.cost_out != nullptr);
     const int tpw = DlShape<N, KMAX, D>::TPW;
-    const bool sc1 = dl_store_sc1((size_t)a.B * KMAX * D * N * sizeof(double), DlShape<N, KMAX, D>::RR);
-    const int64_t blocks = (a.B + tpw - 1) / tpw;
-    if (blocks == 0) return hipSuccess;
+    const size_t out_bytes = (size_t)a.B * KMAX * D * N * sizeof(double);
+    const bool sc1 = dl_store_sc1(out_bytes, DlShape<N, KMAX, D>::RR);
+    if (a.B == 0) return hipSuccess;
     const bool al16 = !(reinterpret_cast<uintptr_t>(a.coeffs) & 15u);
     const int al = al16 ? (sc1 ? 2 : 1) : 0;
-    const void* fn = al == 2 ? (const void*)solve_dl_kernel<N, R, KMAX, D, 2>
-                             : al == 1 ? (const void*)solve_dl_kernel<N, R, KMAX, D, 1> : (const void*)solve_dl_kernel<N, R, KMAX, D, 0>;
-    if (lds > kMaxLdsPerBlock) {  // (long chains keep z' in LDS: beyond the default dynamic limit)
-      const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
+    DlKernArgs ka;
+    if (!dl_fill_hot(N, KMAX, D, tpw, a, &ka.h)) return hipErrorInvalidValue;
+    ka.a = a;
+    const unsigned blocks = ka.h.last_block + 1u;
+    // the status-free instantiation only when nothing it leaves out is asked for (free_out alone
+    // needs none of the checks), and where it is the faster one (dl_status_free)
+    const bool st = a.status || a.cost_out || a.n_free_out || !dl_status_free(out_bytes, DlShape<N, KMAX, D>::RR);
+    if (st) {
+      if (al == 2) return launch_dl_inst<N, R, KMAX, D, 2, true>(ka, blocks, lds, stream);
+      if (al == 1) return launch_dl_inst<N, R, KMAX, D, 1, true>(ka, blocks, lds, stream);
+      return launch_dl_inst<N, R, KMAX, D, 0, true>(ka, blocks, lds, stream);
     }
-    const DlKernArgs ka{a, tpw};
-    if (al == 2)
-      launch_kernel((solve_dl_kernel<N, R, KMAX, D, 2>), dim3((unsigned)blocks), dim3(kBlock), lds, stream, ka);
-    else if (al == 1)
-      launch_kernel((solve_dl_kernel<N, R, KMAX, D, 1>), dim3((unsigned)blocks), dim3(kBlock), lds, stream, ka);
-    else
-      launch_kernel((solve_dl_kernel<N, R, KMAX, D, 0>), dim3((unsigned)blocks), dim3(kBlock), lds, stream, ka);
-    return hipGetLastError();
+    if (al == 2) return launch_dl_inst<N, R, KMAX, D, 2, false>(ka, blocks, lds, stream);
+    if (al == 1) return launch_dl_inst<N, R, KMAX, D, 1, false>(ka, blocks, lds, stream);
+    return launch_dl_inst<N, R, KMAX, D, 0, false>(ka, blocks, lds, stream);
   }
 }
 

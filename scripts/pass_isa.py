@@ -19,9 +19,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mav_trajectory_generation_cmake_amd", "csrc")
 CALLS = {
     "pattern": r"dl_run_pass<DC, AL16>\(c, a, w, E, own, 0, lds, tph\);",
-    "ends": r"dl_ends_pass<N, R, KMAX, D, AL16>\(eown\);",
-    "general": r"dl_general_pass<N, R, KMAX, D, AL16>\(gown\);",
-    "fallback": r"dl_fallback<N, R, D>\(a, w\.pair0, w\.nvt, __builtin_amdgcn_ballot_w64\(fown\), lds\);",
+    "ends": r"dl_ends_pass<N, R, KMAX, D, AL16, ST>\(eown\);",
+    "general": r"dl_general_pass<N, R, KMAX, D, AL16, ST>\(gown\);",
+    "fallback": r"dl_fallback<N, R, D>\(dl_args\(\)\.a, w\.pair0, w\.nvt, __builtin_amdgcn_ballot_w64\(fown\), lds\);",
 }
 
 
@@ -54,8 +54,9 @@ def build(keep, unit, r, src):
         shutil.rmtree(tmp, ignore_errors=True)
     name = "solve_dl_kernelILi%sELi%dELi" % (unit.split("_")[0][1:], r)
     # the instantiation with the 16-B aligned output and plain stores (AL16 = 1; POL env: 2, sc1 stores)
-    m = re.search(r"^(_ZN3mtg15%s\w*ELi%sEEEvNS_10DlKernArgsE):[^\n]*\n(.*?)^\.Lfunc_end"
-                  % (name, os.environ.get("POL", "1")), asm, re.S | re.M)
+    # and the status flag (ST env: 1, the instantiation with the status checks; 0, without them)
+    m = re.search(r"^(_ZN3mtg15%s\w*ELi%sELb%sEEEvNS_10DlKernArgsE):[^\n]*\n(.*?)^\.Lfunc_end"
+                  % (name, os.environ.get("POL", "1"), os.environ.get("ST", "1")), asm, re.S | re.M)
     body = m.group(2)
     lines = body.splitlines()
     isins = [bool(re.match(r"^\s+[a-z_][a-z0-9_.]*\b", l)) and not l.strip().startswith(".") for l in lines]
